@@ -9,9 +9,14 @@ stages of 32, DESIGN.md §3, on one GPU and on several) -- entering argmin, rati
 pivot row and objective row of each -- followed by one sweep that applies their rank-1 updates
 to every stored tableau element.  W untimed steps, then K timed steps: by default the driver's
 window, W = 5 and K = 20 (phase-1 pivots 320..1600 of the first 2000), whose end
-state is checked against the CPU oracle's pin at pivot 1600 (the line's `parity`); --steps 0 times
+state --full checks against the CPU oracle's pin at pivot 1600 (the line's `parity`); --steps 0 times
 up to about pivot 2080.  Every timed step is a full batch, so the timed window runs exactly the kernels
-the warmup ran.
+the warmup ran.  More steps than phase 1 has are timed in laps: each lap a fresh tableau and its own
+W untimed steps, outside the clock.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs DIR if asked and prints the
+JSON line.  Everything below -- the parity check, the secondary workload, the sweep-kernel bench,
+the whole solves and the CPU baseline -- runs only with --full.
 
 N GPUs: the constraint rows are split into N contiguous 512-aligned blocks, each GPU sweeps only
 its rows; per pivot the shards exchange the tile winners and the pivot row (peer memory over
@@ -36,6 +41,7 @@ import json
 import os
 import sys
 import time
+from types import SimpleNamespace
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -91,6 +97,24 @@ def window_parity(config, pivots, d, base):
           "basis_sha256": _sha(base) == pin["sha256_base"]}
     return {"pivots": pivots, "oracle_pin": f"tests/golden/long_pivots.json[{config}] at pivot {pivots}",
             "match": all(ok.values()), **ok}
+
+
+DUMP_TABLEAU_MAX_BYTES = 48 << 20  # (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, sess, m, width, d, base, status):
+    """What a caller of the timed path holds after its last step, as float64 .npy files: the
+    objective row, the basis, the session's pivot count and phase status, and the resident tableau
+    itself where it is small enough (the library reads a tableau back whole or not at all, and
+    config 5's is 19 GB in logical columns)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "objective_row.npy"), np.asarray(d, dtype=np.float64))
+    np.save(os.path.join(path, "basis.npy"), np.asarray(base, dtype=np.float64))
+    np.save(os.path.join(path, "pivots_and_status.npy"), np.array([sess.total_pivots(), status], dtype=np.float64))
+    if 8 * m * width <= DUMP_TABLEAU_MAX_BYTES:
+        np.save(os.path.join(path, "tableau.npy"), sess.tableau(m, width)[0])
 
 
 def solve_parity(name, res):
@@ -173,6 +197,13 @@ def main():
                     help="timed steps; a step = one batch of pivots + one tableau sweep (0 = up to about pivot 2080)")
     ap.add_argument("--warmup", type=int, default=5, help="untimed steps before timing")
     ap.add_argument("--config", default="config5", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (objective row, basis, pivot count and "
+                         "status; the tableau too where it fits in 48 MB) as DIR/<name>.npy (one process only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures and checks: the "
+                         "oracle-pin parity of the run, the secondary workload, the sweep-kernel bench, the whole "
+                         "solves and the CPU baseline (each still selectable by its own option below)")
     ap.add_argument("--batch", type=int, default=0,
                     help="pivots per tableau sweep (0 = library default: 64 from 4096 rows, else 32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -190,6 +221,8 @@ def main():
     ap.add_argument("--no-update-bench", action="store_true",
                     help="skip the synthetic 4096x8192 sweep bench (SURVEY.md §8d config 3')")
     args = ap.parse_args()
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--dump-outputs needs the one-process form (no torchrun)")
 
     import torch
     import torch.distributed as dist
@@ -226,35 +259,59 @@ def main():
         if world > 1:
             dist.barrier()
 
-    def measure(config, steps, warmup, events, last_pivot=2016 + 64):
+    def measure(config, steps, warmup, events, last_pivot=2016 + 64, check=False, dump_dir=None):
         """W untimed + `steps` timed steps (batches of K pivots + one sweep) of `config`'s phase 1;
-        steps = 0: up to pivot `last_pivot`."""
+        steps = 0: up to pivot `last_pivot`.  When phase 1 ends before `steps` steps are timed, the
+        remaining ones are timed on a fresh tableau after its own W untimed steps (another lap; the
+        set-up and the warmup of a lap are outside the clock), so `steps` steps are always timed.
+        check: the end state against the oracle's pin; dump_dir: the end state as .npy files."""
         n, m, seed = CONFIGS[config]
-        t_setup = time.perf_counter()
-        # generateRandomProblem(n, m, seed, 1, 100) synthesised directly in HBM, each rank its rows
-        sess = sx.Session(generated=(n, m, seed, 1, 100))
-        torch.cuda.synchronize()
-        t_setup = time.perf_counter() - t_setup
-        K = sess.batch()  # pivots per step: the library's batch on this engine
-        if steps <= 0:
-            steps = max(1, (last_pivot - warmup * K) // K)
-        if warmup > 0:
-            sess.pivots(warmup * K)
-        barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        tim = sess.pivots(steps * K, time_updates=events)
-        torch.cuda.synchronize()
-        barrier()
-        elapsed = time.perf_counter() - t0
+        summed = ("wall_ms", "update_ms", "pivots", "update_launches", "swept_pivots", "swept_bytes")
+        tim = SimpleNamespace(**{f: 0 for f in summed})
+        elapsed, done, laps = 0.0, 0, 0
+        while True:
+            t_lap = time.perf_counter()
+            # generateRandomProblem(n, m, seed, 1, 100) synthesised directly in HBM, each rank its rows
+            sess = sx.Session(generated=(n, m, seed, 1, 100))
+            torch.cuda.synchronize()
+            if laps == 0:
+                t_setup = time.perf_counter() - t_lap
+                K = sess.batch()  # pivots per step: the library's batch on this engine
+                if steps <= 0:
+                    steps = max(1, (last_pivot - warmup * K) // K)
+            if warmup > 0:
+                sess.pivots(warmup * K)
+            barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lap = sess.pivots((steps - done) * K, time_updates=events)
+            torch.cuda.synchronize()
+            barrier()
+            elapsed += time.perf_counter() - t0
+            if lap.pivots <= 0:
+                raise RuntimeError(f"{config}: no pivot left to time after {warmup} warmup steps")
+            for f in summed:
+                setattr(tim, f, getattr(tim, f) + getattr(lap, f))
+            for f in ("status", "width", "stored_width", "local_rows"):
+                setattr(tim, f, getattr(lap, f))
+            done += -(-lap.pivots // K)  # (the batch that ends the phase may be short: still one step)
+            laps += 1
+            if done >= steps:
+                break
+            sess.close()
+        # bytes per sweep: the mean over the timed sweeps
+        tim.update_bytes = lap.update_bytes if laps == 1 else tim.swept_bytes / max(tim.update_launches, 1)
         if world > 1:
             tt = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
         parity = None
-        if world == 1:  # (outside the timed region: the run's own end state vs the oracle's pin)
+        if world == 1 and (check or dump_dir):  # (outside the timed region)
             d_end, base_end = sess.objective_row_and_basis(m, 1 + n + 2 * m)
-            parity = window_parity(config, (warmup + steps) * K, d_end, base_end)
+            if check and laps == 1:  # the run's own end state vs the oracle's pin
+                parity = window_parity(config, (warmup + steps) * K, d_end, base_end)
+            if dump_dir:
+                dump_outputs(dump_dir, sess, m, 1 + n + 2 * m, d_end, base_end, tim.status)
         # per-rank split of the pivot time: this rank's timed sweeps vs the rest (the chain: the
         # fused batches, slack exchanges and launch gaps), from its own HIP events
         mine = {"rank": rank, "rows": tim.local_rows, "pivots": tim.pivots,
@@ -272,7 +329,7 @@ def main():
         achieved = tim.swept_bytes / (tim.update_ms / 1e3) / 1e9 if tim.update_launches else None
         return {"n": n, "m": m, "seed": seed, "tim": tim, "elapsed": elapsed, "pivots": tim.pivots,
                 "avg_update_s": avg_update_s, "achieved": achieved, "setup_s": t_setup,
-                "steps": steps, "warmup": warmup, "per_rank": per_rank, "K": K, "parity": parity}
+                "steps": steps, "warmup": warmup, "per_rank": per_rank, "K": K, "parity": parity, "laps": laps}
 
     def roofline(cfg, r):
         tim, achieved = r["tim"], r["achieved"]
@@ -338,7 +395,8 @@ def main():
         return (f"{cfg}: phase-1 pivots, {r['m']}x{1 + r['n'] + 2 * r['m']} fp64 tableau "
                 f"(m={r['m']}, n={r['n']}, seed={r['seed']})")
 
-    r = measure(args.config, args.steps, args.warmup, args.update_events)
+    r = measure(args.config, args.steps, args.warmup, args.update_events, check=args.full,
+                dump_dir=args.dump_outputs)
     n, m, seed, tim, elapsed, pivots = r["n"], r["m"], r["seed"], r["tim"], r["elapsed"], r["pivots"]
     K, steps = r["K"], r["steps"]
     out = {
@@ -368,13 +426,14 @@ def main():
             "exchange": exchange_name(),
             "per_rank": r["per_rank"],
             "pivots_timed": pivots, "first_timed_pivot": args.warmup * K, "status_after": tim.status,
-            "setup_s": r["setup_s"],
+            "laps": r["laps"], "setup_s": r["setup_s"],
         },
+        "full": args.full,
         "parity": r["parity"],
         "roofline": roofline(args.config, r),
         "cpu_baseline": None,
     }
-    if args.secondary and args.secondary != args.config:
+    if args.full and args.secondary and args.secondary != args.config:
         r2 = measure(args.secondary, args.secondary_steps, args.secondary_warmup, args.update_events, last_pivot=8960)
         out["secondary"] = {
             "workload": workload(args.secondary, r2),
@@ -387,7 +446,7 @@ def main():
             "status_after": r2["tim"].status, "rows_per_gpu_rank0": r2["tim"].local_rows, "setup_s": r2["setup_s"],
             "roofline": roofline(args.secondary, r2),
         }
-    if n_gpus == 1 and not args.no_update_bench:
+    if args.full and n_gpus == 1 and not args.no_update_bench:
         # SURVEY.md §8d config 3': the sweep kernel alone on a synthetic 4096 x 8192 fp64 matrix
         # (uniform [1,100], seed 823296) with K random pending pivots, K = the pivot loop's batch
         # (three runs of 10 untimed + 50 timed sweeps each; the median run is reported -- the
@@ -429,7 +488,7 @@ def main():
                             "counts Infinity-Cache hits too) -- not measured in this run") if ub_traffic else None,
             out_of_cache=dict(big, traffic=(ub_traffic or {}).get("16384x8192")),
             loop_batch_on_4096_rows=K3, variants=variants)
-    if args.full_solves:
+    if args.full and args.full_solves:
         # the whole drop-in call, as main.cu -t times it: build + both phases + solution (problem
         # synthesised on the GPU and copied to the host first, outside the clock)
         # (at N GPUs: the whole solve on N row-block shards -- every rank calls twoPhaseMethod with
@@ -459,7 +518,7 @@ def main():
                 full["reference_pivots"] = REF_SOLVE[name]["pivots"]
                 full["pivots_match_reference"] = list(res.pivots) == REF_SOLVE[name]["pivots"]
             out["full_solve"].append(full)
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(n, m, seed, CPU_SAMPLE[args.config], sx)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -10,7 +10,7 @@ TAG=${TAG:-ab}
 O=gpurun_out/$TAG
 mkdir -p $O
 REPS=${REPS:-3}
-BENCH_ARGS=${BENCH_ARGS:---steps 20 --warmup 5 --no-cpu-baseline --full-solves=}
+BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5 --no-cpu-baseline --full-solves=}
 for rep in $(seq 1 $REPS); do
   for v in ${VARIANTS:-base=}; do
     name=${v%%=*}; envs=${v#*=}

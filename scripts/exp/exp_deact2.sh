@@ -5,7 +5,7 @@ source "$(dirname "$0")/../gpu_step.sh"
 step suite2 700 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_published.py tests/test_gpu_tabular.py tests/test_gpu_deactivate.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread -m gpu || exit $?
 tail -1 $O/suite2.log
 for v in 1 0 1 0; do
-  export SIMPLEX_DEACTIVATE=$v; step bench_$v 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline || exit $?
+  export SIMPLEX_DEACTIVATE=$v; step bench_$v 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline || exit $?
   python3 - $O/bench_$v.log $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

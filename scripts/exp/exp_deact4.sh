@@ -8,9 +8,9 @@ step deact 400 python -u -m pytest tests/test_gpu_deactivate.py -x -q -p no:cach
 tail -1 $O/deact.log
 step subset 700 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_large.py tests/test_gpu_published.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread -m gpu -k "compaction or two_phase or region or long_pins or whole_solve or published or config2 or session or pivots" || exit $?
 tail -1 $O/subset.log
-step kt 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline || exit $?
+step kt 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline || exit $?
 for v in 8 0 8 0; do
-  export SIMPLEX_DEACTIVATE=$v; step bench_$v 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline || exit $?
+  export SIMPLEX_DEACTIVATE=$v; step bench_$v 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline || exit $?
   python3 - $O/bench_$v.log $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

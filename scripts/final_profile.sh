@@ -9,8 +9,8 @@ O=gpurun_out/${TAG:-prof}
 mkdir -p $O
 PROF_OUT=$O bash scripts/profile_round.sh || exit $?
 echo "== bench (driver's command) ($(date +%T))"
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.log 2>&1 || exit $?
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.log 2>&1 || exit $?
 tail -1 $O/bench_driver.log | cut -c1-300
 echo "== bench (defaults) ($(date +%T))"
-timeout -k 10 400 python3 bench.py > $O/bench_default.log 2>&1 || exit $?
+timeout -k 10 400 python3 bench.py --full > $O/bench_default.log 2>&1 || exit $?
 tail -1 $O/bench_default.log | cut -c1-300

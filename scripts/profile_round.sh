@@ -17,9 +17,9 @@ step() {
     return $rc
 }
 B5="--gpus 1 --steps 20 --warmup 5"
-step kt 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run -- python3 bench.py $B5 || exit $?
+step kt 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run -- python3 bench.py --full $B5 || exit $?
 for c in FETCH_SIZE WRITE_SIZE; do
-  step $c 200 rocprofv3 --pmc $c --output-format csv -d $O/$c -o run -- python3 bench.py $B5 --no-cpu-baseline --full-solves= || exit $?
+  step $c 200 rocprofv3 --pmc $c --output-format csv -d $O/$c -o run -- python3 bench.py --full $B5 --no-cpu-baseline --full-solves= || exit $?
 done
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 GRBM_GUI_ACTIVE"
 step sq 200 rocprofv3 --pmc $SQ --output-format csv -d $O/sq -o run -- python3 bench.py $B5 --no-cpu-baseline --full-solves= --secondary= --no-update-bench || exit $?
