@@ -26,12 +26,28 @@ def same(a, b):
 
 
 # ------------------------------------------------------------------ argmin tree
-@pytest.mark.parametrize("L", [1, 2, 31, 32, 33, 511, 512, 513, 4097, 16384, 73728, 100000])
+_ARGMIN_LENGTHS = [1, 2, 31, 32, 33, 511, 512, 513, 4097, 16384, 73728, 100000,
+                   261633, 262144]  # 511 tiles + 1; the 512-tile ceiling of the 512-thread pass 2
+
+
+@pytest.mark.parametrize("L", _ARGMIN_LENGTHS)
 def test_dev_argmin_matches_oracle(gpu, L):
     rng = np.random.default_rng(L)
     v = rng.integers(-4, 4, size=L).astype(np.float64)
     v[rng.integers(0, L, size=max(1, L // 5))] += rng.choice([3e-10, -7e-10, 2e-9], size=max(1, L // 5))
     assert sx.dev_argmin(v) == oracle.argmin(v)
+
+
+@pytest.mark.parametrize("L", _ARGMIN_LENGTHS)
+def test_dev_argmin_ladder_matches_oracle(gpu, L):
+    """a vector that is one ladder, -(3 + 0.125e-9 k) at every position: from 4097 on the oracle's
+    index is not np.argmin's (tests/test_tie_ladders.py), so the tree order decides"""
+    from tie_ladders import ladder_vector
+    v = ladder_vector(L)
+    ref = oracle.argmin(v)
+    if L >= 4097:
+        assert ref[0] != int(np.argmin(v))
+    assert sx.dev_argmin(v) == ref
 
 
 def test_dev_argmin_all_max(gpu):
