@@ -71,10 +71,16 @@ void simplex_set_alias(int on);
  * an untouched unit vector, so it is kept past the swept block of the tableau and skipped by
  * every sweep -- bit-identical results; active only when no row is negated (b >= 0) */
 void simplex_set_compact(int on);
-/* with slack compaction on one shard: every `every` sweeps (default 8; 0 off) the swept slack
- * columns whose slack is basic -- exact unit vectors, checked bit for bit -- are moved past the swept
- * block too, and moved back when their row leaves; bit-identical results */
+/* with slack compaction: every `every` sweeps (default 8; 0 off) the swept slack columns whose
+ * slack is basic -- exact unit vectors, checked bit for bit -- are moved past the swept block too,
+ * and moved back when their row leaves; bit-identical results.  On one shard, and on the row-block
+ * shards of one process (virtual ranks, a SIMPLEX_GPUS / simplex_set_gpus device list), which
+ * combine their per-row-block checks before any of them moves a column.  RCCL ranks with world > 1
+ * and IPC-mode sessions do not deactivate. */
 void simplex_set_deactivate(int every);
+/* the same on the several shards of one process: 1 on (default), 0 only on one shard (the earlier
+ * rule; for A/B runs and for bisecting on multi-GPU hardware) */
+void simplex_set_deactivate_shards(int on);
 /* one shard: run each batch of pivots as ONE resident launch (ratio tiles + objective-row tiles
  * handing off through write-through records) instead of two launches per pivot;
  * -1 auto (default: when the grid fits the device), 0 off */
@@ -200,6 +206,9 @@ double simplex_session_objective(simplex_session *s);   /* d[0] */
 long long simplex_session_tableau(simplex_session *s, double *T, long long ld, double *d, int *base);
 /* slack columns the sweeps currently move (m without slack compaction) */
 long long simplex_session_active_slacks(simplex_session *s);
+/* the same per shard of this process: returns the number of shards and copies the first `cap`
+ * shards' swept slack counts to out (equal on every shard: the permutation is replicated) */
+int simplex_session_shard_active_slacks(simplex_session *s, long long *out, int cap);
 long long simplex_session_total_pivots(simplex_session *s);
 /* pivots per batch (and per sweep) of simplex_session_pivots on this session */
 int simplex_session_batch(simplex_session *s);

@@ -98,6 +98,7 @@ SIGNATURES = {
     "simplex_set_alias": (None, [ctypes.c_int]),
     "simplex_set_compact": (None, [ctypes.c_int]),
     "simplex_set_deactivate": (None, [ctypes.c_int]),
+    "simplex_set_deactivate_shards": (None, [ctypes.c_int]),
     "simplex_set_fused": (None, [ctypes.c_int]),
     "simplex_last_phase_seconds": (None, [ctypes.POINTER(ctypes.c_double)]),
     "simplex_last_objective_row": (ctypes.c_longlong, [ctypes.POINTER(ctypes.c_double), ctypes.c_longlong]),
@@ -137,6 +138,7 @@ SIGNATURES = {
                                                     ctypes.c_longlong, ctypes.POINTER(ctypes.c_double),
                                                     ctypes.POINTER(ctypes.c_int)]),
     "simplex_session_active_slacks": (ctypes.c_longlong, [ctypes.c_void_p]),
+    "simplex_session_shard_active_slacks": (ctypes.c_int, [ctypes.c_void_p, c_ll_p, ctypes.c_int]),
     "simplex_session_total_pivots": (ctypes.c_longlong, [ctypes.c_void_p]),
     "simplex_session_batch": (ctypes.c_int, [ctypes.c_void_p]),
     "simplex_session_launch_log": (ctypes.c_longlong, [ctypes.c_void_p, c_ll_p, c_double_p, ctypes.c_longlong]),

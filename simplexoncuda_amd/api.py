@@ -256,6 +256,14 @@ class Session:
         """Slack columns the sweeps move (m without slack compaction)."""
         return self._lib.simplex_session_active_slacks(self._h)
 
+    def shard_active_slacks(self):
+        """The same on every shard of this process, in rank order (they agree: the slack
+        permutation is replicated)."""
+        out = np.zeros(64, dtype=np.int64)
+        w = self._lib.simplex_session_shard_active_slacks(
+            self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), out.size)
+        return [int(v) for v in out[:w]]
+
     def total_pivots(self):
         return self._lib.simplex_session_total_pivots(self._h)
 
@@ -375,9 +383,16 @@ DEACTIVATE_EVERY = 8  # the engine's default
 
 
 def set_deactivate(every):
-    """With slack compaction on one shard: every `every` sweeps (default 8; 0 off) the swept slack
-    columns whose slack is basic (exact unit vectors) leave the swept block."""
+    """With slack compaction: every `every` sweeps (default 8; 0 off) the swept slack columns whose
+    slack is basic (exact unit vectors) leave the swept block -- on one shard and on the shards of
+    one process (virtual ranks, a device list), which combine their checks first; not on RCCL ranks
+    with world > 1 or IPC sessions."""
     _lib.load().simplex_set_deactivate(int(every))
+
+
+def set_deactivate_shards(on):
+    """set_deactivate on the several shards of one process too (default 1; 0: one shard only)."""
+    _lib.load().simplex_set_deactivate_shards(1 if on else 0)
 
 
 def set_fused(mode):

@@ -207,8 +207,9 @@ void sx_launch_sweep(double *T, int rows, int row0, size_t ld, TLay tl, int Ns, 
 void sx_launch_activate(int *perm, int *iperm, int *ucol, const int *urow, int *nact, int m, double *T, int rows,
                         int row0, size_t ld, TLay tl, int s0, const Pending &pd, const DevState *st, int slots,
                         hipStream_t s);  // slots: the batch size (two passes above SX_HMAX)
-// one shard, after a sweep (every few batches): the swept slack columns whose slack is basic (exact
-// unit vectors, checked) moved behind the swept block (k_deact_*)
+// after a sweep (every few batches): the swept slack columns whose slack is basic (exact unit
+// vectors, checked) moved behind the swept block (k_deact_*) -- on one shard, or on
+// the row-block shards of one process, which plan from their combined verdicts (DeactPeers)
 #define SX_DEACT_CAP 4096  // columns per round (a multiple of 1024)
 struct DeactList {
     int C;    // listed columns (swept slacks that are basic), stored-position order
@@ -220,9 +221,20 @@ struct DeactList {
 // column with its unit vector first -- required: an entered column is e_r only where its entries'
 // residuals a_k - fl(a_k / p) p round to 0; fail: [m] slack -> 1 + the row it failed the check in, zero
 // at allocation)
+// peers = false: the whole round on one shard.  peers = true: only the list and this shard's check
+// (mark / list / check); once every shard's check has finished, sx_launch_deactivate_apply plans from
+// all the shards' verdicts and moves this shard's rows
 void sx_launch_deactivate(int *perm, int *iperm, int *ucol, int *urow, int *nact, const int *base, int n, int m,
                           bool alias, double *T, int rows, int row0, TLay tl, int s0, unsigned long long *tag,
-                          unsigned epoch, bool check, int *fail, DeactList *L, hipStream_t s);
+                          unsigned epoch, bool check, int *fail, DeactList *L, hipStream_t s, bool peers = false);
+// the shards' verdict arrays (DeactList::bad of every shard of the process, rank order; this
+// shard's own among them), passed to k_deact_plan by value
+struct DeactPeers {
+    const int *bad[SX_MAXW];
+    int nw;
+};
+void sx_launch_deactivate_apply(int *perm, int *iperm, int *ucol, int *urow, int *nact, double *T, int rows, int row0,
+                                TLay tl, int s0, int *fail, DeactList *L, const DeactPeers &peers, hipStream_t s);
 // fused batch of up to k pivots on one shard (ratio tiles + objective tiles in one resident
 // grid); returns false (nothing launched) when the grid cannot be resident at once
 bool sx_batch_fits(int rows, Cols c, int k);

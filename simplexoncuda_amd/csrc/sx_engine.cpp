@@ -65,7 +65,8 @@ struct Config {
     int alias = 1;           // store phase-1 artificial columns as their slack columns
     int compact = 1;         // sweep only the slack columns pivots have touched (when exact)
     int deact = -1;          // ... and move the swept slacks that are basic out of the sweep every `deact`
-                             // sweeps (one shard; 0 off; -1: SIMPLEX_DEACTIVATE=k, else 8)
+                             // sweeps (0 off; -1: SIMPLEX_DEACTIVATE=k, else 8)
+    int deact_shards = 1;    // ... on the several shards of one process too (0: on one shard only)
     int mr_single_launch = 1;  // virtual shards: all ranks' fused batches as one launch (0: one per stream)
     int regions = 1;         // two-region tableau layout (TLay): 0 off, 1 auto (aliasing, m > 4096),
                              // >= 2: region A holds that many slack positions (test hook)
@@ -297,7 +298,7 @@ struct Shard {
     int *ucol = nullptr;              //   row r -> the unswept slack column that is e_r, or -1 [m]
     int *urow = nullptr;              //   unswept slack k -> the row of its unit vector [m]
     int *nact = nullptr;              //   swept slack columns (the swept block's width past 1+n)
-    DeactList *dlist = nullptr;       //   basic slacks moved out of the sweep (one shard)
+    DeactList *dlist = nullptr;       //   basic slacks moved out of the sweep (its `bad` read by every shard's plan)
     unsigned long long *dtag = nullptr;  // its scratch: stored slack offset -> (round, basic row) [m]
     unsigned dround = 0;                 //   rounds run
     int *dfail = nullptr;                //   slack -> 1 + the row whose check it failed [m]
@@ -1173,6 +1174,20 @@ class Engine {
         SX_HIP(hipStreamSynchronize(s));
         return v;
     }
+    // the same on every shard of this process (at most cap copied); returns their number
+    int shard_active_slacks(long long *out, int cap) {
+        for (size_t i = 0; i < sh.size() && (int)i < cap; ++i) {
+            Shard &x = sh[i];
+            int v = m;
+            if (compact) {
+                DevGuard g(x.dev);
+                SX_HIP(hipMemcpyAsync(&v, x.nact, sizeof(int), hipMemcpyDeviceToHost, x.s));
+                SX_HIP(hipStreamSynchronize(x.s));
+            }
+            out[i] = v;
+        }
+        return (int)sh.size();
+    }
 
     // ---------------------------------------------------------------- one pivot
     SweepCfg sweep_cfg(int batch) const {
@@ -1430,18 +1445,53 @@ class Engine {
         }
         if (rec_shard0) sx_set_sweep_record(nullptr);
         if (ev1) SX_HIP(hipEventRecord(ev1, s));
-        // one shard, every g_cfg.deact sweeps: the swept slacks whose columns are exactly their unit
-        // vectors leave the swept block.  (Not on several shards: each sees only its rows of a column,
-        // and the shards would have to agree on every check -- a column that entered keeps the
-        // residuals a_k - fl(a_k / p) p where they are not 0)
+        // every g_cfg.deact sweeps: the swept slacks whose columns are exactly their unit vectors leave
+        // the swept block.  One shard runs the round by itself.  The shards of one process (virtual
+        // ranks, a device list; W <= SX_MAXW) each see only their rows of a column, and a column that
+        // entered keeps the residuals a_k - fl(a_k / p) p where they are not 0, so
+        // they plan from the OR of all their checks (simplex_set_deactivate_shards(0): one shard only,
+        // as before).  RCCL ranks with world > 1 and IPC sessions do not deactivate: their verdicts
+        // would need a collective that nothing here can exercise.
         if (g_cfg.deact < 0) {
             const char *e = getenv("SIMPLEX_DEACTIVATE");
             g_cfg.deact = e ? (atoi(e) > 0 ? atoi(e) : 0) : 8;
         }
-        if (compact && W == 1 && g_cfg.deact > 0 && (sweeps + 1) % g_cfg.deact == 0 && m <= 65536) {
-            Shard &x = sh[0];
-            sx_launch_deactivate(x.perm, x.iperm, x.ucol, x.urow, x.nact, x.base, n, m, cols(N).art0 != 0x7fffffff, x.T,
-                                 x.rows, x.row0, tl, 1 + n, x.dtag, ++x.dround, true, x.dfail, x.dlist, x.s);
+        const bool shards_ok = W == 1 || (g_cfg.deact_shards && !rccl && W <= SX_MAXW);
+        if (compact && shards_ok && g_cfg.deact > 0 && (sweeps + 1) % g_cfg.deact == 0 && m <= 65536) {
+            const bool al = cols(N).art0 != 0x7fffffff;
+            if (W == 1) {
+                Shard &x = sh[0];
+                sx_launch_deactivate(x.perm, x.iperm, x.ucol, x.urow, x.nact, x.base, n, m, al, x.T, x.rows, x.row0, tl,
+                                     1 + n, x.dtag, ++x.dround, true, x.dfail, x.dlist, x.s);
+            } else {
+                // No host wait; two orderings across the shards' streams.
+                // (1) Every plan sees every finished check.  Shards on one device share that device's
+                //     engine stream (x.s), so all their checks are enqueued here before any of their
+                //     plans below and stream order does it; across devices join() makes every device
+                //     stream wait (events) for everything enqueued so far on the others -- their checks.
+                // (2) A shard's next k_deact_list, which clears its `bad`, starts after every plan of
+                //     this round has read it: on one device the next round is enqueued behind this
+                //     round's plans on the same stream; across devices the second join() makes every
+                //     device stream wait for the others' plans (and moves) before anything later.
+                // No kernel writes a `bad` array between its shard's check and the next list: the
+                // plans combine in registers (k_deact_plan).
+                DeactPeers peers;
+                std::memset(&peers, 0, sizeof(peers));
+                peers.nw = W;
+                for (auto &x : sh) {
+                    DevGuard g(x.dev);
+                    peers.bad[x.rank] = x.dlist->bad;  // (an address; device memory is not read here)
+                    sx_launch_deactivate(x.perm, x.iperm, x.ucol, x.urow, x.nact, x.base, n, m, al, x.T, x.rows, x.row0, tl,
+                                         1 + n, x.dtag, ++x.dround, true, x.dfail, x.dlist, x.s, true);
+                }
+                join();
+                for (auto &x : sh) {
+                    DevGuard g(x.dev);
+                    sx_launch_deactivate_apply(x.perm, x.iperm, x.ucol, x.urow, x.nact, x.T, x.rows, x.row0, tl, 1 + n, x.dfail,
+                                               x.dlist, peers, x.s);
+                }
+                join();
+            }
         }
         ++sweeps;
         q_host = 0;
@@ -2036,6 +2086,7 @@ void simplex_set_regions(int mode) { g_cfg.regions = mode < 0 ? 1 : mode; }
 void simplex_set_mr_single_launch(int on) { g_cfg.mr_single_launch = on ? 1 : 0; }
 void simplex_set_compact(int on) { g_cfg.compact = on ? 1 : 0; }
 void simplex_set_deactivate(int every) { g_cfg.deact = every > 0 ? every : 0; }
+void simplex_set_deactivate_shards(int on) { g_cfg.deact_shards = on ? 1 : 0; }
 void simplex_set_fused(int mode) { g_cfg.fused = mode < 0 ? -1 : (mode ? 1 : 0); }
 void simplex_set_p2p(int mode) { g_cfg.p2p = mode < 0 ? -1 : (mode ? 1 : 0); }
 int simplex_p2p_ready(void) {
@@ -2360,6 +2411,9 @@ long long simplex_session_tableau(simplex_session *S, double *T, long long ld, d
 }
 
 long long simplex_session_active_slacks(simplex_session *S) { return S->E->active_slacks(); }
+int simplex_session_shard_active_slacks(simplex_session *S, long long *out, int cap) {
+    return S->E->shard_active_slacks(out, out ? cap : 0);
+}
 long long simplex_session_total_pivots(simplex_session *S) { return S->E->read_state().pivots; }
 int simplex_session_batch(simplex_session *S) {
     const int K = S->E->batch_size();

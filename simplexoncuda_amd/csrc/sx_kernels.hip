@@ -3019,7 +3019,8 @@ __global__ __launch_bounds__(256) void k_activate(int *__restrict__ perm, int *_
     if (t == 0) *nact_p = na0 + s_added;
 }
 
-// Basic slack columns out of the sweep (one shard; after a sweep, every few batches).  When a variable
+// Basic slack columns out of the sweep (after a sweep, every few batches; one shard, or the row-block
+// shards of one process -- see "several shards" below).  When a variable
 // enters at row r the reference (solver.cu:34-46) makes its pivot-row entry p / p = 1 and every other
 // entry fma(-(a_k / p), p, a_k) = a_k - fl(a_k / p) p, rounded once: +0 wherever fl(a_k / p) p == a_k,
 // a residual of an ulp or so elsewhere.  A column whose residuals all vanished is exactly the unit
@@ -3042,6 +3043,17 @@ __global__ __launch_bounds__(256) void k_activate(int *__restrict__ perm, int *_
 //                  ucol / urow / nact updated;
 //   k_deact_move   the exchanges on T: the other column copied to the candidate's position, e_r
 //                  written at the candidate's new one.
+// Several shards (the shards of one process: virtual ranks or a device list; not RCCL ranks, not IPC
+// sessions): the basis and the permutation are replicated, so k_deact_mark / k_deact_list build the
+// same list on every shard, but k_deact_check sees only the shard's rows of a column -- a column
+// that re-entered may keep its residuals in one row block alone.  k_deact_plan therefore forms its
+// verdict from every shard's `bad` array (DeactPeers, by value: a listed column failed if any
+// shard's rows failed it; a shard without rows launches no check and its cleared array says "no
+// failure"), in registers: no `bad` array is written after its shard's check, so a peer's plan may
+// read it at any time until the next round's k_deact_list clears it.  Every shard then plans the
+// same exchanges (perm / iperm / ucol / urow / nact / fail stay replicated) and k_deact_move applies
+// them to its own rows.  The launch site (Engine::enqueue_sweep) orders check -> every plan ->
+// next list across the shards' streams.
 __device__ __forceinline__ int deact_slack(int v, int n, int m, bool alias) {
     if (v >= n && v < n + m) return v - n;
     if (alias && v >= n + m && v < n + 2 * m) return v - n - m;  // (an artificial is stored as its slack)
@@ -3143,7 +3155,8 @@ __global__ __launch_bounds__(256) void k_deact_check(const double *__restrict__ 
 
 __global__ __launch_bounds__(1024) void k_deact_plan(int *__restrict__ perm, int *__restrict__ iperm,
                                                      int *__restrict__ ucol, int *__restrict__ urow,
-                                                     int *__restrict__ nact_p, int *__restrict__ fail, DeactList *L) {
+                                                     int *__restrict__ nact_p, int *__restrict__ fail, DeactList *L,
+                                                     DeactPeers peers) {
     __shared__ int s_w[16];
     __shared__ int s_free[SX_DEACT_CAP];           // tail positions that receive a candidate
     __shared__ unsigned s_tail[SX_DEACT_CAP / 32];  // tail positions held by a candidate (bits)
@@ -3155,7 +3168,13 @@ __global__ __launch_bounds__(1024) void k_deact_plan(int *__restrict__ perm, int
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int j = PER * t + q;
-        ok[q] = j < C && L->bad[j] == 0;
+        // the shards' verdicts combined: failed if any shard's rows failed it (system-scope loads:
+        // a peer's array may live on another device)
+        int bad = 0;
+        if (j < C)
+            for (int w = 0; w < peers.nw; ++w)
+                bad |= __hip_atomic_load(peers.bad[w] + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        ok[q] = j < C && bad == 0;
         nok += ok[q];
         if (j < C && !ok[q]) fail[iperm[L->x[j]]] = L->r[j] + 1;  // (not listed again while basic there)
     }
@@ -3522,14 +3541,26 @@ void sx_launch_activate(int *perm, int *iperm, int *ucol, const int *urow, int *
 
 void sx_launch_deactivate(int *perm, int *iperm, int *ucol, int *urow, int *nact, const int *base, int n, int m,
                           bool alias, double *T, int rows, int row0, TLay tl, int s0, unsigned long long *tag,
-                          unsigned epoch, bool check, int *fail, DeactList *L, hipStream_t s) {
+                          unsigned epoch, bool check, int *fail, DeactList *L, hipStream_t s, bool peers) {
     if (m <= 0) return;
     if (m > 65536) SX_FATAL("basic-slack deactivation: at most 65536 slacks");
     const int g = rows > 0 ? (rows + 255) / 256 : 1;
     k_deact_mark<<<(m + 255) / 256, 256, 0, s>>>(base, perm, nact, n, m, alias, fail, tag, epoch);
     k_deact_list<<<1, 1024, 0, s>>>(nact, tag, epoch, L);
     if (check && rows > 0) k_deact_check<<<g, 256, 0, s>>>(T, rows, row0, tl, s0, L);
-    k_deact_plan<<<1, 1024, 0, s>>>(perm, iperm, ucol, urow, nact, fail, L);
+    if (!peers) {  // one shard: its own verdict, the round in one call
+        DeactPeers own = {};
+        own.nw = 1;
+        own.bad[0] = L->bad;
+        sx_launch_deactivate_apply(perm, iperm, ucol, urow, nact, T, rows, row0, tl, s0, fail, L, own, s);
+    }
+}
+
+void sx_launch_deactivate_apply(int *perm, int *iperm, int *ucol, int *urow, int *nact, double *T, int rows, int row0,
+                                TLay tl, int s0, int *fail, DeactList *L, const DeactPeers &peers, hipStream_t s) {
+    if (peers.nw < 1 || peers.nw > SX_MAXW) SX_FATAL("basic-slack deactivation: 1 .. SX_MAXW verdict arrays");
+    const int g = rows > 0 ? (rows + 255) / 256 : 1;
+    k_deact_plan<<<1, 1024, 0, s>>>(perm, iperm, ucol, urow, nact, fail, L, peers);
     if (rows > 0) k_deact_move<<<g, 256, 0, s>>>(T, rows, row0, tl, s0, L);
 }
 
