@@ -162,6 +162,29 @@ void simplex_set_first_batch_id(unsigned int id);
 int twoPhaseMethodEx(problem_t *problem, double *solution, double *optimalValue, int *base_out,
                      long long *pivots_out, long long max_pivots);
 
+/* ---- batched solve: many small LPs in one resident launch ---- */
+/* every problem's twoPhaseMethodEx result, solved together; per-problem outputs:
+ * status_out[count], opt_out[count], pivots_out[count][2]; solutions[k] (vars doubles) and
+ * base_out[k] (constraints ints) may be NULL as arrays or per entry.  Returns 0, <0 on bad arguments.
+ * A problem whose working set fits a compute unit's LDS, or a 4 MiB slice of device memory, is
+ * solved whole by one workgroup; larger ones go through the engine inside the same call, so every
+ * shape is accepted.  Results are bit-identical to twoPhaseMethodEx either way (solutions[k] and
+ * opt_out[k] are written only for a FEASIBLE problem; max_pivots as in twoPhaseMethodEx).  Runs on
+ * the current device (simplex_set_device) and ignores the shard settings (SIMPLEX_GPUS,
+ * simplex_set_gpus, virtual ranks); count == 0 is valid.  What simplex_last_objective_row and
+ * simplex_last_phase_seconds report after a batch call is unspecified. */
+int simplex_solve_batch(problem_t *const *problems, int count, long long max_pivots, int *status_out,
+                        double *const *solutions, double *opt_out, int *const *base_out, long long *pivots_out);
+/* where a problem of this shape would run: 2 LDS-resident, 1 workspace-resident, 0 engine; host arithmetic only */
+int simplex_batch_class(int n, int m);
+/* of the last simplex_solve_batch call: out[0] LDS-resident, out[1] workspace-resident, out[2] engine
+ * (too large), out[3] evicted to the engine after exhausting the resident budget (these are also
+ * counted in out[0] or out[1], where they started) */
+void simplex_batch_counts(long long out[4]);
+/* resident pivot budget per phase (0 = default formula, 64 + 16 (n + m)); test hook and safety valve:
+ * a resident problem that needs more pivots is re-solved from scratch by the engine, uncapped */
+void simplex_set_batch_budget(long long pivots);
+
 /* problem_t from caller arrays (copied; A column-major m x n); free with freeProblem()
  * and then free() of the struct, as the reference's callers do. */
 problem_t *simplex_problem_from_arrays(int n, int m, const double *A_colmajor, const double *b,

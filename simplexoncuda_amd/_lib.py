@@ -119,6 +119,11 @@ SIGNATURES = {
     "simplex_set_replicated_objective": (None, [ctypes.c_int]),
     "simplex_set_blocked": (None, [ctypes.c_int]),
     "twoPhaseMethodEx": (ctypes.c_int, [P_PROBLEM, c_double_p, c_double_p, c_int_p, c_ll_p, ctypes.c_longlong]),
+    "simplex_solve_batch": (ctypes.c_int, [ctypes.POINTER(P_PROBLEM), ctypes.c_int, ctypes.c_longlong, c_int_p,
+                                           ctypes.POINTER(c_double_p), c_double_p, ctypes.POINTER(c_int_p), c_ll_p]),
+    "simplex_batch_class": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "simplex_batch_counts": (None, [c_ll_p]),
+    "simplex_set_batch_budget": (None, [ctypes.c_longlong]),
     "simplex_problem_from_arrays": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "simplex_generate_problem_ex": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int]),

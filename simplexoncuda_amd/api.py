@@ -171,6 +171,60 @@ def twoPhaseMethodEx(problem, max_pivots=-1):
     return Result(st, x[:problem.n], opt.value, base[:problem.m], (piv[0], piv[1]))
 
 
+def solve_batch(problems, max_pivots=-1):
+    """twoPhaseMethodEx of every Problem of a sequence, solved together (simplex_solve_batch): small
+    problems run whole inside resident workgroups of one launch, larger ones on the engine; the
+    results are bit-identical to twoPhaseMethodEx's, in the order of `problems`."""
+    lib = _lib.load()
+    problems = list(problems)
+    count = len(problems)
+    if any(not p.ptr for p in problems):
+        raise ValueError("solve_batch: a Problem is closed")
+    ptrs = (_lib.P_PROBLEM * max(count, 1))(*[p.ptr for p in problems])
+    shapes = [(p.n, p.m) for p in problems]
+    # one buffer for every solution and one for every basis; the per-problem pointers are addresses
+    xoff = np.zeros(count + 1, dtype=np.int64)
+    boff = np.zeros(count + 1, dtype=np.int64)
+    if count:
+        xoff[1:] = np.cumsum([max(n, 1) for n, _ in shapes])
+        boff[1:] = np.cumsum([max(m, 1) for _, m in shapes])
+    xs = np.zeros(max(int(xoff[-1]), 1))
+    bases = np.zeros(max(int(boff[-1]), 1), dtype=np.int32)
+    xp = (xs.ctypes.data + 8 * xoff).astype(np.uint64)
+    bp = (bases.ctypes.data + 4 * boff).astype(np.uint64)
+    status = np.zeros(max(count, 1), dtype=np.int32)
+    opt = np.zeros(max(count, 1))
+    piv = np.zeros((max(count, 1), 2), dtype=np.int64)
+    rc = lib.simplex_solve_batch(ptrs, count, max_pivots, _ip(status), xp.ctypes.data_as(ctypes.POINTER(_lib.c_double_p)),
+                                 _dp(opt), bp.ctypes.data_as(ctypes.POINTER(_lib.c_int_p)),
+                                 piv.ctypes.data_as(_lib.c_ll_p))
+    if rc < 0:
+        raise ValueError(f"simplex_solve_batch: bad arguments ({rc})")
+    return [Result(int(status[k]), xs[xoff[k]:xoff[k] + n].copy(), float(opt[k]), bases[boff[k]:boff[k] + m].copy(),
+                   (int(piv[k, 0]), int(piv[k, 1])))
+            for k, (n, m) in enumerate(shapes)]
+
+
+def batch_class(n, m):
+    """Where solve_batch runs a problem of n variables and m constraints: 2 LDS-resident,
+    1 workspace-resident, 0 the engine (host arithmetic only)."""
+    return _lib.load().simplex_batch_class(int(n), int(m))
+
+
+def batch_counts():
+    """Of the last solve_batch call: (LDS-resident, workspace-resident, engine because too large,
+    evicted to the engine after exhausting the resident pivot budget)."""
+    out = (ctypes.c_longlong * 4)()
+    _lib.load().simplex_batch_counts(out)
+    return tuple(int(v) for v in out)
+
+
+def set_batch_budget(p):
+    """Resident pivot budget per phase of solve_batch (0: the default, 64 + 16 (n + m)); a problem
+    that needs more is re-solved by the engine, so results do not depend on it."""
+    _lib.load().simplex_set_batch_budget(int(p))
+
+
 def last_objective_row():
     """The last twoPhaseMethod call's final objective row (simplex_last_objective_row)."""
     lib = _lib.load()

@@ -1,0 +1,296 @@
+// sx_batch.hip -- batched solve: one 512-thread workgroup carries one whole LP
+// through the two-phase method without a host round trip, then takes the next problem of the
+// launch from a global work counter.  No workgroup ever waits for another: the only
+// synchronisation is __syncthreads().
+//
+// Per problem the kernel performs, in order, exactly the operations of the serial restatement of
+// the reference (oracle/simplex_oracle.c orc_two_phase): the same IEEE operations on the same
+// operands and the reference's epsilon-argmin tree (sx_argmin.hpp) for both selections, so every
+// result is bit-identical to twoPhaseMethodEx.  Compiled with -ffp-contract=off; every fused
+// multiply-add is an explicit fma().
+//
+// The kernel is a template over where the working set (sx_common.hpp BatchLay) lives: dynamic LDS,
+// or a per-workgroup slice of a device buffer.  The artificial column of row k stays bit-identical
+// to its slack column (sx_common.hpp Cols), so T stores 1 + n + m columns and logical column
+// j >= 1 + n + m reads stored column j - m; d keeps the full width.
+
+#include <float.h>
+
+#include "sx_argmin.hpp"
+#include "sx_common.hpp"
+
+namespace {
+
+#define SX_EVICTED (-100)  // phase result inside the kernel: the resident budget ran out
+
+struct BatchWork {
+    double *T, *d, *prow, *colE;
+    TilePart *parts;
+    int *base;
+    int n, m, ld;
+};
+
+// orc_argmin over val(0) .. val(L - 1): per 512-wide tile the per-thread grid-stride pre-combine and
+// block_argmin512, then pass 2 over the tile winners when there is more than one tile.  The
+// workgroup walks the tiles one after the other.  Result in every thread.
+template <class F>
+__device__ __forceinline__ void wg_argmin(int L, F val, TilePart *parts, double *s_v, int *s_i, double *s_rv,
+                                          int *s_ri, double &v_out, int &i_out) {
+    const int tiles = L > SX_TILE ? (L + SX_TILE - 1) / SX_TILE : 1;
+    for (int b = 0; b < tiles; ++b) {
+        double v = DBL_MAX;
+        int i = -1;
+        for (int idx = b * SX_TILE + (int)threadIdx.x; idx < L; idx += SX_TILE * tiles) {
+            const double c = val(idx);
+            if (cmp_eps(c, v) < 0) {
+                v = c;
+                i = idx;
+            }
+        }
+        block_argmin512(v, i, s_v, s_i);
+        if (threadIdx.x == 0) {
+            if (tiles == 1) {
+                *s_rv = v;
+                *s_ri = i;
+            } else {
+                parts[b].v = v;
+                parts[b].idx = i;
+                parts[b].elig = 0;
+            }
+        }
+        __syncthreads();
+    }
+    if (tiles > 1) {
+        double v;
+        int i;
+        stage2_512(parts, tiles, v, i, s_v, s_i);
+        if (threadIdx.x == 0) {
+            *s_rv = v;
+            *s_ri = i;
+        }
+        __syncthreads();
+    }
+    v_out = *s_rv;
+    i_out = *s_ri;
+}
+
+// orc_update_objective at width N: coef[i] = d[1 + base[i]] snapshot (kept in colE), then per column
+// the 512-row block partials from 0.0 in ascending row order, added left to right, d[j] -= s.
+__device__ __forceinline__ void wg_update_objective(const BatchWork &w, int N) {
+    const int art0 = 1 + w.n + w.m;
+    for (int i = threadIdx.x; i < w.m; i += SX_TILE) w.colE[i] = w.d[1 + w.base[i]];
+    __syncthreads();
+    for (int j = threadIdx.x; j < N; j += SX_TILE) {
+        const double *col = w.T + (j >= art0 ? j - w.m : j);
+        double s = 0.0;
+        for (int i0 = 0; i0 < w.m; i0 += SX_TILE) {
+            const int i1 = i0 + SX_TILE < w.m ? i0 + SX_TILE : w.m;
+            double p = 0.0;
+            for (int i = i0; i < i1; ++i) p = fma(col[(size_t)i * w.ld], w.colE[i], p);
+            s = i0 == 0 ? p : s + p;
+        }
+        w.d[j] = w.d[j] - s;
+    }
+    __syncthreads();
+}
+
+// orc_solve at width N: pivots until the phase ends, the cap is reached (SX_PIVOT_CAP) or one more
+// pivot would exceed the resident budget (SX_EVICTED).  Uniform over the workgroup.
+__device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max_pivots, long long budget,
+                                        long long &pivots, double *s_v, int *s_i, double *s_rv, int *s_ri) {
+    const int n = w.n, m = w.m, ld = w.ld, Ns = 1 + n + m, art0 = Ns;
+    // the row update gives each row to 16, 32 or 64 consecutive lanes (a row sweep by consecutive
+    // lanes is conflict-free at any stride; narrow tableaux keep more rows in flight)
+    const int g = Ns <= 16 ? 4 : Ns <= 32 ? 5 : 6;
+    const int G = 1 << g, RP = SX_TILE >> g;
+    const int rl = (int)threadIdx.x >> g, cl = (int)threadIdx.x & (G - 1);
+    long long k = 0;
+    for (;;) {
+        if (max_pivots >= 0 && k >= max_pivots) {
+            pivots = k;
+            return SX_PIVOT_CAP;
+        }
+        double dmin;
+        int e;
+        wg_argmin(N - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, s_v, s_i, s_rv, s_ri, dmin, e);
+        if (!(cmp_eps(dmin, 0.0) < 0)) {
+            pivots = k;
+            return SX_FEASIBLE;
+        }
+        const int ce = 1 + e >= art0 ? 1 + e - m : 1 + e;  // stored column of the entering variable
+        int any = 0;
+        for (int i = threadIdx.x; i < m; i += SX_TILE) {
+            const double a = w.T[(size_t)i * ld + ce];
+            w.colE[i] = a;
+            any |= a >= SX_EPS;
+        }
+        any = __syncthreads_or(any);
+        if (!any) {
+            pivots = k;
+            return SX_UNBOUNDED;
+        }
+        if (k >= budget) {
+            pivots = k;
+            return SX_EVICTED;
+        }
+        double rv;
+        int r;
+        wg_argmin(
+            m,
+            [&](int i) {
+                const double a = w.colE[i], b = w.T[(size_t)i * ld];
+                return cmp_eps(a, 0.0) > 0 ? b / a : DBL_MAX;
+            },
+            w.parts, s_v, s_i, s_rv, s_ri, rv, r);
+        if (r < 0 || r >= m) {
+            pivots = k;
+            return SX_NUMERIC_FAIL;
+        }
+        // pivot row copy and row factors -(a_ie / p); T is not written before the barrier
+        const double *rowr = w.T + (size_t)r * ld;
+        const double p = rowr[ce];
+        for (int j = threadIdx.x; j < Ns; j += SX_TILE) w.prow[j] = rowr[j];
+        for (int i = threadIdx.x; i < m; i += SX_TILE) w.colE[i] = -w.colE[i] / p;
+        if (threadIdx.x == 0) w.base[r] = e;
+        __syncthreads();
+        for (int i = rl; i < m; i += RP) {
+            double *row = w.T + (size_t)i * ld;
+            if (i == r) {
+                for (int j = cl; j < Ns; j += G) row[j] = w.prow[j] / p;
+            } else {
+                const double f = w.colE[i];
+                for (int j = cl; j < Ns; j += G) row[j] = fma(f, w.prow[j], row[j]);
+            }
+        }
+        const double fd = -dmin / p;
+        for (int j = threadIdx.x; j < N; j += SX_TILE) w.d[j] = fma(fd, w.prow[j >= art0 ? j - m : j], w.d[j]);
+        __syncthreads();
+        ++k;
+    }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE) void k_batch_solve(BatchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    __shared__ double s_v[16];
+    __shared__ int s_i[16];
+    __shared__ double s_rv;
+    __shared__ int s_ri;
+    __shared__ unsigned s_k;
+    double *W;
+    if constexpr (LDS)
+        W = s_dyn;
+    else
+        W = a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    for (;;) {
+        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const unsigned k = s_k;
+        if (k >= (unsigned)a.count) return;
+        const int id = a.order[k];
+        const BatchProb pb = a.probs[id];
+        const int n = pb.n, m = pb.m;
+        const BatchLay lay = sx_batch_lay(n, m);
+        BatchWork w;
+        w.T = W;
+        w.d = W + lay.d;
+        w.prow = W + lay.prow;
+        w.colE = W + lay.colE;
+        w.parts = reinterpret_cast<TilePart *>(W + lay.parts);
+        w.base = reinterpret_cast<int *>(W + lay.base);
+        w.n = n;
+        w.m = m;
+        w.ld = lay.ld;
+        const int ld = lay.ld, Ns = 1 + n + m, N1 = Ns + m;
+        const double *A = a.in + pb.in_off, *bv = A + (size_t)n * m, *cv = bv + m;
+        const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+
+        // orc_build_phase1: RHS, A, slack (the artificial block aliases it); a row with
+        // compare(b_i) < 0 is negated across all its entries, zeros included
+        for (int x = threadIdx.x; x < n * m; x += SX_TILE) {
+            const int j = x / m, i = x - j * m;
+            const double v = A[x];
+            w.T[(size_t)i * ld + 1 + j] = cmp_eps(bv[i], 0.0) < 0 ? -v : v;
+        }
+        for (int x = threadIdx.x; x < m * (m + 1); x += SX_TILE) {
+            const int i = x / (m + 1), t = x - i * (m + 1);
+            const double b = bv[i];
+            const double v = t == 0 ? b : (t - 1 == i ? 1.0 : 0.0);
+            w.T[(size_t)i * ld + (t == 0 ? 0 : n + t)] = cmp_eps(b, 0.0) < 0 ? -v : v;
+        }
+        for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j <= n + m ? 0.0 : 1.0;
+        for (int i = threadIdx.x; i < m; i += SX_TILE) w.base[i] = n + m + i;
+        __syncthreads();
+
+        long long p1 = 0, p2 = 0;
+        int status;
+        wg_update_objective(w, N1);
+        const int st1 = wg_solve(w, N1, a.max_pivots, budget, p1, s_v, s_i, &s_rv, &s_ri);
+        if (st1 == SX_PIVOT_CAP || st1 == SX_NUMERIC_FAIL || st1 == SX_EVICTED) {
+            status = st1;
+        } else if (cmp_eps(w.d[0], 0.0) < 0) {
+            status = SX_INFEASIBLE;
+        } else {
+            int art = 0;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) art |= w.base[i] >= n + m && w.base[i] < n + 2 * m;
+            status = __syncthreads_or(art) ? SX_DEGENERATE : SX_FEASIBLE;
+        }
+        if (status == SX_FEASIBLE) {
+            // phase 2: costs -c, slack costs 0, d[0] kept; canonicalise at width 1 + n + m and solve
+            for (int j = threadIdx.x; j < n; j += SX_TILE) w.d[1 + j] = -cv[j];
+            for (int j = threadIdx.x; j < m; j += SX_TILE) w.d[1 + n + j] = 0.0;
+            __syncthreads();
+            wg_update_objective(w, Ns);
+            status = wg_solve(w, Ns, a.max_pivots, budget, p2, s_v, s_i, &s_rv, &s_ri);
+        }
+        // (every path above ends behind a barrier, so T, d and base are complete here)
+        double *out = a.out + pb.out_off;
+        int *base_out = reinterpret_cast<int *>(out + m);
+        for (int i = threadIdx.x; i < m; i += SX_TILE) {
+            out[i] = w.T[(size_t)i * ld];
+            base_out[i] = w.base[i];
+        }
+        if (threadIdx.x == 0) {
+            BatchRes r;
+            r.opt = w.d[0];
+            r.p1 = p1;
+            r.p2 = p2;
+            r.status = status == SX_EVICTED ? SX_NOT_ENDED : status;
+            r.evicted = status == SX_EVICTED ? 1 : 0;
+            a.res[id] = r;
+        }
+        __syncthreads();  // the next problem overwrites the working set and s_k
+    }
+}
+
+}  // namespace
+
+int sx_batch_resident(bool lds, size_t lds_bytes) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        SX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch_solve<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, SX_BATCH_LDS_BYTES));
+        attr_set = true;
+    }
+    int dev = 0, cus = 0, per_cu = 0;
+    SX_HIP(hipGetDevice(&dev));
+    SX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (lds)
+        SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve<true>, SX_TILE, lds_bytes));
+    else
+        SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve<false>, SX_TILE, 0));
+    if (per_cu < 1) SX_FATAL("the batch kernel does not fit a compute unit");
+    return per_cu * cus;
+}
+
+void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    if (grid < 1 || a.count < 1) return;
+    if (lds) {
+        if (lds_bytes > SX_BATCH_LDS_BYTES) SX_FATAL("batch kernel: working set exceeds the LDS class");
+        k_batch_solve<true><<<grid, SX_TILE, lds_bytes, s>>>(a);
+    } else {
+        if (a.ws == nullptr || a.slice < 1) SX_FATAL("batch kernel: no workspace");
+        k_batch_solve<false><<<grid, SX_TILE, 0, s>>>(a);
+    }
+    SX_HIP(hipGetLastError());
+}

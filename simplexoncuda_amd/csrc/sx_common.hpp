@@ -306,3 +306,77 @@ void sx_launch_gen_vector(uint32_t seed, long long first, int count, double lo, 
 
 void sx_launch_argmin_vector(const double *v, long long L, TilePart *parts, int *out_idx, double *out_v,
                              hipStream_t s);
+
+// ---- batched solve: one workgroup carries one whole LP (sx_batch.hip) ----
+// Dynamic LDS a resident workgroup may claim: the CU's 160 KiB less 512 bytes for the kernel's
+// static reduction scratch.  A problem whose working set fits is LDS-resident (class 2).
+#define SX_BATCH_LDS_BYTES (160 * 1024 - 512)
+// Workspace-resident cap (class 1): a working set of at most this many doubles (4 MiB) in a
+// per-workgroup slice of device memory; larger problems go to the engine (class 0).
+#define SX_BATCH_WS_DOUBLES (1 << 19)
+// ... and all the slices of one launch together take at most this many bytes
+#define SX_BATCH_WS_BYTES (1ull << 30)
+// Default resident pivot budget per phase (simplex_set_batch_budget(0)); ordinary small instances
+// need n + m to 2 (n + m) pivots.
+__host__ __device__ constexpr long long sx_batch_default_budget(int n, int m) {
+    return 64 + 16 * ((long long)n + (long long)m);
+}
+
+// Working set of one resident problem, in doubles from its start: T (m rows of the 1 + n + m stored
+// columns at an odd stride ld), d at the full phase-1 width 1 + n + 2m, the pivot-row copy, colE,
+// the argmin tile winners and the basis.  Every offset is even (TilePart is 16-byte aligned).
+struct BatchLay {
+    int ld;
+    long long d, prow, colE, parts, base, total;
+};
+__host__ __device__ constexpr long long sx_even(long long x) { return (x + 1) & ~1LL; }
+__host__ __device__ constexpr BatchLay sx_batch_lay(int n, int m) {
+    const long long Ns = 1 + (long long)n + m, N1 = Ns + m;
+    const long long ld = Ns | 1;
+    const long long L = (N1 - 1 > m ? N1 - 1 : m), tiles = (L + SX_TILE - 1) / SX_TILE;
+    BatchLay l{};
+    l.ld = (int)ld;
+    l.d = sx_even(ld * m);
+    l.prow = l.d + sx_even(N1);
+    l.colE = l.prow + sx_even(Ns);
+    l.parts = l.colE + sx_even(m);
+    l.base = l.parts + 2 * tiles;
+    l.total = l.base + sx_even((m + 1) / 2);
+    return l;
+}
+// 2 LDS-resident, 1 workspace-resident, 0 engine (also every shape without a variable or a constraint)
+__host__ __device__ constexpr int sx_batch_class(int n, int m) {
+    if (n < 1 || m < 1) return 0;
+    const long long t = sx_batch_lay(n, m).total;
+    return t * 8 <= SX_BATCH_LDS_BYTES ? 2 : t <= SX_BATCH_WS_DOUBLES ? 1 : 0;
+}
+
+// One resident problem of a batch call: its shape and where its input (A column-major, b, c) and
+// its output (the final RHS column, then the basis as ints) lie, in doubles from the buffers' starts.
+struct __attribute__((aligned(16))) BatchProb {
+    int n, m;
+    long long in_off, out_off;
+    long long pad;
+};
+struct __attribute__((aligned(16))) BatchRes {
+    double opt;
+    long long p1, p2;
+    int status;
+    int evicted;  // 1: the resident budget ran out; the host re-solves the problem on the engine
+};
+struct BatchArgs {
+    const BatchProb *probs;
+    const int *order;   // [count] problems of this launch, larger first
+    int count;
+    unsigned *counter;  // the launch's work counter (zero at launch)
+    const double *in;
+    BatchRes *res;
+    double *out;
+    double *ws;         // workspace-resident: the slices; null for the LDS class
+    long long slice;    // doubles per slice
+    long long max_pivots;  // per phase, < 0: none (status SX_PIVOT_CAP)
+    long long budget;      // resident pivots per phase, 0: sx_batch_default_budget
+};
+// workgroups of the batch kernel the current device holds at once with this much dynamic LDS
+int sx_batch_resident(bool lds, size_t lds_bytes);
+void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s);

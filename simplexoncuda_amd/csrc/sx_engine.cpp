@@ -2203,6 +2203,202 @@ int twoPhaseMethodEx(problem_t *problem, double *solution, double *optimalValue,
     return two_phase(problem, solution, optimalValue, base_out, pivots_out, max_pivots);
 }
 
+// ---------------------------------------------------------------- batched solve
+// Small problems are solved whole by resident workgroups (sx_batch.hip), one launch per storage
+// class; what is too large for them, or ran out of its resident pivot budget, goes through
+// two_phase() one by one.  One upload and one download per call; the device buffers are plain
+// allocations kept between calls and grown on demand.
+static long long g_batch_budget = 0;
+static long long g_batch_counts[4] = {0, 0, 0, 0};
+static std::mutex g_batch_mu;
+static struct {
+    int dev = -1;
+    void *in = nullptr, *out = nullptr, *ws = nullptr;
+    size_t in_bytes = 0, out_bytes = 0, ws_bytes = 0;
+    std::vector<unsigned char> up, down;  // host staging (pageable), kept too: no page faults per call
+} g_bb;
+
+static void batch_reserve(void **p, size_t *have, size_t need) {
+    if (need <= *have) return;
+    if (*p != nullptr) SX_HIP(hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    SX_HIP(hipMalloc(p, need));
+    *have = need;
+}
+
+int simplex_batch_class(int n, int m) { return sx_batch_class(n, m); }
+void simplex_batch_counts(long long out[4]) {
+    for (int k = 0; k < 4; ++k) out[k] = g_batch_counts[k];
+}
+void simplex_set_batch_budget(long long pivots) { g_batch_budget = pivots > 0 ? pivots : 0; }
+
+int simplex_solve_batch(problem_t *const *problems, int count, long long max_pivots, int *status_out,
+                        double *const *solutions, double *opt_out, int *const *base_out, long long *pivots_out) {
+    if (count < 0 || (count > 0 && problems == nullptr)) return -1;
+    for (int k = 0; k < count; ++k)
+        if (problems[k] == nullptr || problems[k]->vars < 0 || problems[k]->constraints < 0) return -2;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    for (long long &c : g_batch_counts) c = 0;
+    if (count == 0) return 0;
+    if (g_cfg.device >= 0) SX_HIP(hipSetDevice(g_cfg.device));
+    int dev = 0;
+    SX_HIP(hipGetDevice(&dev));
+
+    // launches: the LDS class in two bins (working sets that let 2 workgroups share a CU -- the
+    // kernel's registers allow no more -- or 1; each launch sized to the largest problem of its
+    // bin), then the workspace class
+    const size_t lds_bin[2] = {160 * 1024 / 2 - 512, SX_BATCH_LDS_BYTES};
+    std::vector<int> resident, engine, bin[3];  // resident[id] = index in `problems`; bin: ids
+    std::vector<BatchProb> probs;
+    std::vector<long long> need;  // working set of resident problem id, doubles
+    size_t in_doubles = 0, out_doubles = 0;
+    for (int k = 0; k < count; ++k) {
+        const int n = problems[k]->vars, m = problems[k]->constraints;
+        const int cls = sx_batch_class(n, m);
+        if (cls == 0) {
+            engine.push_back(k);
+            ++g_batch_counts[2];
+            continue;
+        }
+        const long long t = sx_batch_lay(n, m).total;
+        const int id = (int)resident.size();
+        int b = 2;
+        if (cls == 2)
+            for (b = 0; (size_t)t * 8 > lds_bin[b]; ++b) {
+            }
+        bin[b].push_back(id);
+        ++g_batch_counts[cls == 2 ? 0 : 1];
+        BatchProb pb{};
+        pb.n = n;
+        pb.m = m;
+        pb.in_off = (long long)in_doubles;
+        pb.out_off = (long long)out_doubles;
+        in_doubles += (size_t)n * m + (size_t)m + (size_t)n;
+        out_doubles += (size_t)m + (size_t)(m + 1) / 2;
+        probs.push_back(pb);
+        need.push_back(t);
+        resident.push_back(k);
+    }
+    const size_t R = resident.size();
+    if (R > 0) {
+        if (g_bb.dev != dev) {  // (the buffers of another device are given up)
+            for (void **p : {&g_bb.in, &g_bb.out, &g_bb.ws})
+                if (*p != nullptr) {
+                    SX_HIP(hipFree(*p));
+                    *p = nullptr;
+                }
+            g_bb.in_bytes = g_bb.out_bytes = g_bb.ws_bytes = 0;
+            g_bb.dev = dev;
+        }
+        // upload: [work counters (zero), one per launch] [problem records] [launch orders] [A, b, c of every problem]
+        const size_t off_probs = 16, off_order = off_probs + R * sizeof(BatchProb);
+        const size_t off_in = round_up(off_order + R * sizeof(int), 16);
+        const size_t in_bytes = off_in + in_doubles * sizeof(double);
+        if (g_bb.up.size() < in_bytes) g_bb.up.resize(in_bytes);
+        unsigned char *up = g_bb.up.data();
+        std::memset(up, 0, off_in);
+        std::memcpy(up + off_probs, probs.data(), R * sizeof(BatchProb));
+        int *order = reinterpret_cast<int *>(up + off_order);
+        size_t start[3], pos = 0;
+        for (int b = 0; b < 3; ++b) {  // larger problems first
+            std::stable_sort(bin[b].begin(), bin[b].end(),
+                             [&](int x, int y) { return need[(size_t)x] > need[(size_t)y]; });
+            start[b] = pos;
+            for (int id : bin[b]) order[pos++] = id;
+        }
+        double *in = reinterpret_cast<double *>(up + off_in);
+        for (size_t id = 0; id < R; ++id) {
+            const problem_t *P = problems[resident[id]];
+            const size_t n = (size_t)P->vars, m = (size_t)P->constraints;
+            double *dst = in + probs[id].in_off;
+            std::memcpy(dst, P->constraintsMatrix, sizeof(double) * n * m);
+            std::memcpy(dst + n * m, P->knownTermsVector, sizeof(double) * m);
+            std::memcpy(dst + n * m + m, P->objectiveFunction, sizeof(double) * n);
+        }
+        const size_t off_out = R * sizeof(BatchRes), out_bytes = off_out + out_doubles * sizeof(double);
+        batch_reserve(&g_bb.in, &g_bb.in_bytes, in_bytes);
+        batch_reserve(&g_bb.out, &g_bb.out_bytes, out_bytes);
+        SX_HIP(hipMemcpy(g_bb.in, up, in_bytes, hipMemcpyHostToDevice));
+        unsigned char *din = static_cast<unsigned char *>(g_bb.in), *dout = static_cast<unsigned char *>(g_bb.out);
+        BatchArgs a{};
+        a.probs = reinterpret_cast<const BatchProb *>(din + off_probs);
+        a.in = reinterpret_cast<const double *>(din + off_in);
+        a.res = reinterpret_cast<BatchRes *>(dout);
+        a.out = reinterpret_cast<double *>(dout + off_out);
+        a.max_pivots = max_pivots;
+        a.budget = g_batch_budget;
+        for (int b = 0; b < 3; ++b) {
+            if (bin[b].empty()) continue;
+            const long long big = need[(size_t)bin[b][0]];
+            a.order = reinterpret_cast<const int *>(din + off_order) + start[b];
+            a.count = (int)bin[b].size();
+            a.counter = reinterpret_cast<unsigned *>(din) + b;
+            if (b < 2) {
+                a.ws = nullptr;
+                a.slice = 0;
+                const size_t lds = (size_t)big * sizeof(double);
+                sx_launch_batch_solve(true, a, std::min(a.count, sx_batch_resident(true, lds)), lds, nullptr);
+            } else {
+                const size_t slice_bytes = (size_t)big * sizeof(double);
+                const long long fit = (long long)std::max<size_t>(1, SX_BATCH_WS_BYTES / slice_bytes);
+                const int grid = (int)std::min<long long>(std::min(a.count, sx_batch_resident(false, 0)), fit);
+                batch_reserve(&g_bb.ws, &g_bb.ws_bytes, slice_bytes * (size_t)grid);
+                a.ws = static_cast<double *>(g_bb.ws);
+                a.slice = big;
+                sx_launch_batch_solve(false, a, grid, 0, nullptr);
+            }
+        }
+        if (g_bb.down.size() < out_bytes) g_bb.down.resize(out_bytes);
+        const unsigned char *down = g_bb.down.data();
+        SX_HIP(hipMemcpy(g_bb.down.data(), g_bb.out, out_bytes, hipMemcpyDeviceToHost));
+        const BatchRes *res = reinterpret_cast<const BatchRes *>(down);
+        const double *out = reinterpret_cast<const double *>(down + off_out);
+        for (size_t id = 0; id < R; ++id) {
+            const int k = resident[id];
+            if (res[id].evicted) {
+                engine.push_back(k);
+                ++g_batch_counts[3];
+                continue;
+            }
+            const int n = probs[id].n, m = probs[id].m;
+            const double *rhs = out + probs[id].out_off;
+            const int *base = reinterpret_cast<const int *>(rhs + m);
+            if (status_out) status_out[k] = res[id].status;
+            if (pivots_out) {
+                pivots_out[2 * k] = res[id].p1;
+                pivots_out[2 * k + 1] = res[id].p2;
+            }
+            if (base_out && base_out[k]) std::memcpy(base_out[k], base, sizeof(int) * (size_t)m);
+            if (res[id].status == SX_FEASIBLE) {  // getSolutionHost (:370-383)
+                if (opt_out) opt_out[k] = res[id].opt;
+                if (solutions && solutions[k]) {
+                    for (int j = 0; j < n; ++j) solutions[k][j] = 0.0;
+                    for (int i = 0; i < m; ++i)
+                        if (base[i] < n) solutions[k][base[i]] = rhs[i];
+                }
+            }
+        }
+    }
+    // the engine path: one shard on this device whatever the shard settings say, no TIMER CSVs
+    const bool save_single = g_cfg.single_shard, save_nt = g_cfg.no_timer;
+    g_cfg.single_shard = true;
+    g_cfg.no_timer = true;
+    for (int k : engine) {
+        long long piv[2] = {0, 0};
+        const int st = two_phase(problems[k], solutions ? solutions[k] : nullptr, opt_out ? &opt_out[k] : nullptr,
+                                 base_out ? base_out[k] : nullptr, piv, max_pivots);
+        if (status_out) status_out[k] = st;
+        if (pivots_out) {
+            pivots_out[2 * k] = piv[0];
+            pivots_out[2 * k + 1] = piv[1];
+        }
+    }
+    g_cfg.single_shard = save_single;
+    g_cfg.no_timer = save_nt;
+    return 0;
+}
+
 // ---------------------------------------------------------------- tabular_t API
 // tabular.cu:25-39.  The caller fills the tableau itself, so every one of its 1+n+2m columns is
 // stored (no artificial-column aliasing: the caller's artificial columns need not equal the
