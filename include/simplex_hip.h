@@ -185,6 +185,51 @@ void simplex_batch_counts(long long out[4]);
  * a resident problem that needs more pivots is re-solved from scratch by the engine, uncapped */
 void simplex_set_batch_budget(long long pivots);
 
+/* ---- device-resident batched solve: device arrays in, device arrays out, no host copy ---- */
+/* count problems of ONE shape (n variables x m constraints, simplex_batch_class(n, m) 2 or 1; larger
+ * shapes belong to simplex_solve_batch), read in place from device memory through element strides
+ * and solved by the same resident workgroups; every per-problem result is written to dense device
+ * arrays by the kernel itself.  The call only enqueues on `stream` (two small memsets and one
+ * launch) on the current device: it allocates nothing, copies nothing, never synchronises and keeps
+ * no state, so calls on different streams with different outputs and workspaces are independent.
+ * The inputs are not written; outputs and workspace must not overlap them or each other.
+ * Per problem the results are twoPhaseMethodEx's: status, pivots (phase 1, phase 2) and base as
+ * there; for a FEASIBLE problem opt and x bit for bit, for any other status opt is a quiet NaN and
+ * x is all +0.0 (never stale memory).  objrow[k] is what simplex_last_objective_row reports for
+ * that problem: row_width[k] = 1+n+m entries after phase 2, 1+n+2m when phase 1 ended the solve,
+ * and +0.0 from row_width[k] up to 1+n+2m.
+ * A problem that exhausts the resident pivot budget (simplex_set_batch_budget) is NOT re-solved
+ * here: it is left with status SIMPLEX_NOT_ENDED, opt NaN, x zero and row_width 0, and counted in
+ * *evicted; the caller re-solves it with twoPhaseMethodEx (no other path gives NOT_ENDED).
+ * Shard settings are ignored, as in simplex_solve_batch. */
+typedef struct {
+    int n, m, count;                       /* every problem n variables x m constraints */
+    const double *A; long long A_sb, A_sr, A_sc;   /* element strides: batch, row (constraint), column (variable) */
+    const double *b; long long b_sb, b_si;
+    const double *c; long long c_sb, c_sj;
+    long long max_pivots;                  /* as twoPhaseMethodEx */
+    /* outputs, device memory, dense: */
+    int *status;          /* [count] */
+    long long *pivots;    /* [count][2] */
+    double *opt;          /* [count] */
+    double *x;            /* [count][n]        or NULL */
+    int *base;            /* [count][m]        or NULL */
+    double *objrow;       /* [count][1+n+2m]   or NULL */
+    int *row_width;       /* [count]           or NULL */
+    int *evicted;         /* [1]: problems left SIMPLEX_NOT_ENDED by the resident budget */
+    void *workspace; long long workspace_bytes;   /* 16-byte aligned; simplex_batch_device_workspace bytes */
+    void *stream;         /* hipStream_t; NULL = the null stream */
+} simplex_batch_device_t;
+
+/* bytes of workspace a call of this shape and count needs on the current device (a header with the
+ * work counter; for class 1 also one working-set slice per resident workgroup); -1 for count < 0,
+ * -3 for n < 1, m < 1 or a class-0 shape -- both decided before any device is touched */
+long long simplex_batch_device_workspace(int n, int m, int count);
+/* returns 0 (count == 0: nothing is launched), -1 args NULL or count < 0, -3 shape (as above),
+ * -2 a required pointer is NULL (A, b, c, status, pivots, opt, evicted), -4 a stride of 0 on a
+ * dimension longer than 1, -5 workspace NULL, misaligned or too small */
+int simplex_solve_batch_device(const simplex_batch_device_t *args);
+
 /* problem_t from caller arrays (copied; A column-major m x n); free with freeProblem()
  * and then free() of the struct, as the reference's callers do. */
 problem_t *simplex_problem_from_arrays(int n, int m, const double *A_colmajor, const double *b,

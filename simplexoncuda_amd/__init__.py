@@ -12,6 +12,6 @@ from .api import (  # noqa: F401
     DEACTIVATE_EVERY, set_alias, set_batch, set_compact, set_deactivate, set_deactivate_shards, set_exchange_mode, set_force_exchange, set_fused, set_mr_single_launch,
     set_blocked, set_fine_pivot_rows, set_gpus, set_p2p, set_regions, set_replicated_objective, set_sweep_mfma,
     set_update_waves, set_verbose, set_virtual_ranks,
-    batch_class, batch_counts, set_batch_budget, solve_batch,
+    BatchTensors, batch_class, batch_counts, set_batch_budget, solve_batch, solve_batch_tensors,
     twoPhaseMethod, twoPhaseMethodEx)
 from ._lib import LIB_PATH, load  # noqa: F401

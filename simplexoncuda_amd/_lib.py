@@ -58,6 +58,22 @@ class TimingT(ctypes.Structure):
     ]
 
 
+class BatchDeviceT(ctypes.Structure):
+    """simplex_batch_device_t (include/simplex_hip.h); every pointer is a device address."""
+    _fields_ = [
+        ("n", ctypes.c_int), ("m", ctypes.c_int), ("count", ctypes.c_int),
+        ("A", ctypes.c_void_p), ("A_sb", ctypes.c_longlong), ("A_sr", ctypes.c_longlong), ("A_sc", ctypes.c_longlong),
+        ("b", ctypes.c_void_p), ("b_sb", ctypes.c_longlong), ("b_si", ctypes.c_longlong),
+        ("c", ctypes.c_void_p), ("c_sb", ctypes.c_longlong), ("c_sj", ctypes.c_longlong),
+        ("max_pivots", ctypes.c_longlong),
+        ("status", ctypes.c_void_p), ("pivots", ctypes.c_void_p), ("opt", ctypes.c_void_p), ("x", ctypes.c_void_p),
+        ("base", ctypes.c_void_p), ("objrow", ctypes.c_void_p), ("row_width", ctypes.c_void_p),
+        ("evicted", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_longlong),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
 P_PROBLEM = ctypes.POINTER(ProblemT)
 P_TABULAR = ctypes.POINTER(TabularT)
 
@@ -124,6 +140,8 @@ SIGNATURES = {
     "simplex_batch_class": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "simplex_batch_counts": (None, [c_ll_p]),
     "simplex_set_batch_budget": (None, [ctypes.c_longlong]),
+    "simplex_batch_device_workspace": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "simplex_solve_batch_device": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT)]),
     "simplex_problem_from_arrays": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "simplex_generate_problem_ex": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int]),

@@ -205,6 +205,133 @@ def solve_batch(problems, max_pivots=-1):
             for k, (n, m) in enumerate(shapes)]
 
 
+@dataclass
+class BatchTensors:
+    """solve_batch_tensors' results: device tensors, one row per problem.  For a problem that is not
+    FEASIBLE optimal_value is NaN and its solution row is zero; objective_row (when asked for) holds
+    row_width[k] entries of problem k's final objective row, zero-padded to 1 + n + 2m."""
+    status: object         # int32 [B]
+    pivots: object         # int64 [B, 2]: phase 1, phase 2
+    optimal_value: object  # float64 [B]
+    solution: object       # float64 [B, n]
+    base: object           # int32 [B, m]
+    objective_row: object  # float64 [B, 1 + n + 2m], or None
+    row_width: object      # int32 [B], or None
+    evicted: object        # int; the device tensor (int32 [1]) with finish=False
+
+    @property
+    def reduced_costs(self):
+        """objective_row[:, 1 : 1+n] (a view): (A^T y - c)_j after a FEASIBLE solve."""
+        n = self.solution.shape[1]
+        return self.objective_row[:, 1:1 + n]
+
+    @property
+    def duals(self):
+        """objective_row[:, 1+n : 1+n+m] (a view): the dual y_i of constraint i after a FEASIBLE solve."""
+        n, m = self.solution.shape[1], self.base.shape[1]
+        return self.objective_row[:, 1 + n:1 + n + m]
+
+
+def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True):
+    """twoPhaseMethodEx of B problems of one shape held in device tensors (simplex_solve_batch_device):
+    A [B, m, n], b [B, m], c [B, n], float64 on one ROCm device, read in place through their strides
+    (a transposed or sliced view is not copied).  One launch on torch's current stream of that device
+    solves them in resident workgroups and writes the results on the device: a BatchTensors.
+
+    A problem that exhausts the resident pivot budget (set_batch_budget) is left NOT_ENDED by the
+    kernel and counted in `evicted`.  finish=True (default) reads that count (one 4-byte copy, which
+    waits for the stream) and re-solves such problems through twoPhaseMethodEx, so every result is
+    twoPhaseMethodEx's whatever the budget; finish=False returns right after the enqueue, without
+    synchronising, and `evicted` is the device tensor.  Shapes with batch_class(n, m) == 0 are
+    refused: solve_batch takes those."""
+    import torch
+
+    for name, t in (("A", A), ("b", b), ("c", c)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"solve_batch_tensors: {name} must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype != torch.float64:
+            raise TypeError(f"solve_batch_tensors: {name} must be float64, not {t.dtype}")
+    if A.dim() != 3 or b.dim() != 2 or c.dim() != 2:
+        raise ValueError("solve_batch_tensors: A must be [B, m, n], b [B, m] and c [B, n]")
+    B, m, n = A.shape
+    if tuple(b.shape) != (B, m) or tuple(c.shape) != (B, n):
+        raise ValueError(f"solve_batch_tensors: A is {tuple(A.shape)}, so b must be {(B, m)} and c {(B, n)}; "
+                         f"got {tuple(b.shape)} and {tuple(c.shape)}")
+    if B >= 2 ** 31:
+        raise ValueError("solve_batch_tensors: too many problems for one call")
+    if n < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+        raise ValueError(f"solve_batch_tensors: a problem of {n} variables x {m} constraints is not solved by a "
+                         "resident workgroup; use solve_batch for such shapes")
+    if A.device.type != "cuda":
+        raise ValueError(f"solve_batch_tensors: A is on {A.device}; the tensors must be on a GPU")
+    if b.device != A.device or c.device != A.device:
+        raise ValueError("solve_batch_tensors: A, b and c must be on the same device")
+    lib = _lib.load()
+    dev = A.device
+    N1 = 1 + n + 2 * m
+    with torch.cuda.device(dev):
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        pivots = torch.empty((B, 2), dtype=torch.int64, device=dev)
+        opt = torch.empty(B, dtype=torch.float64, device=dev)
+        x = torch.empty((B, n), dtype=torch.float64, device=dev)
+        base = torch.empty((B, m), dtype=torch.int32, device=dev)
+        row = torch.empty((B, N1), dtype=torch.float64, device=dev) if objective_row else None
+        width = torch.empty(B, dtype=torch.int32, device=dev) if objective_row else None
+        evicted = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int32, device=dev)  # (the call zeroes it)
+        if B > 0:
+            ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
+            if ws_bytes < 0:
+                raise ValueError(f"simplex_batch_device_workspace: bad arguments ({ws_bytes})")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            args = _lib.BatchDeviceT(
+                n=n, m=m, count=B,
+                A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
+                b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
+                c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1),
+                max_pivots=max_pivots,
+                status=status.data_ptr(), pivots=pivots.data_ptr(), opt=opt.data_ptr(), x=x.data_ptr(),
+                base=base.data_ptr(), objrow=row.data_ptr() if objective_row else None,
+                row_width=width.data_ptr() if objective_row else None, evicted=evicted.data_ptr(),
+                workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
+                stream=torch.cuda.current_stream(dev).cuda_stream)
+            rc = lib.simplex_solve_batch_device(ctypes.byref(args))
+            if rc < 0:
+                raise ValueError(f"simplex_solve_batch_device: bad arguments ({rc})")
+        out = BatchTensors(status, pivots, opt, x, base, row, width, evicted)
+        if not finish:
+            return out
+        out.evicted = int(evicted.item()) if B > 0 else 0
+        if out.evicted:
+            _finish_evicted(out, A, b, c, max_pivots)
+    return out
+
+
+def _finish_evicted(out, A, b, c, max_pivots):
+    """Re-solve the problems the kernel left NOT_ENDED through twoPhaseMethodEx and write their
+    results into the output tensors in the kernel's conventions."""
+    import torch
+
+    dev = out.status.device
+    n = out.solution.shape[1]
+    for k in torch.nonzero(out.status == NOT_ENDED).flatten().tolist():
+        p = Problem.from_arrays(A[k].cpu().numpy(), b[k].cpu().numpy(), c[k].cpu().numpy())
+        try:
+            r = twoPhaseMethodEx(p, max_pivots)
+            d = last_objective_row()
+        finally:
+            p.close()
+        feasible = r.status == FEASIBLE
+        out.status[k] = r.status
+        out.pivots[k] = torch.tensor(r.pivots, dtype=torch.int64, device=dev)
+        out.base[k] = torch.from_numpy(r.base).to(dev)
+        out.optimal_value[k] = r.optimal_value if feasible else float("nan")
+        out.solution[k] = torch.from_numpy(r.solution if feasible else np.zeros(n)).to(dev)
+        if out.objective_row is not None:
+            out.objective_row[k].zero_()
+            out.objective_row[k, :len(d)] = torch.from_numpy(d).to(dev)
+            out.row_width[k] = len(d)
+
+
 def batch_class(n, m):
     """Where solve_batch runs a problem of n variables and m constraints: 2 LDS-resident,
     1 workspace-resident, 0 the engine (host arithmetic only)."""

@@ -13,6 +13,10 @@
 // or a per-workgroup slice of a device buffer.  The artificial column of row k stays bit-identical
 // to its slack column (sx_common.hpp Cols), so T stores 1 + n + m columns and logical column
 // j >= 1 + n + m reads stored column j - m; d keeps the full width.
+//
+// Two entries share the device functions: k_batch_solve (simplex_solve_batch: ragged problems packed
+// by the host, results finished on the host) and k_batch_solve_dev (simplex_solve_batch_device: one
+// shape, strided device arrays in, every result written by the kernel).
 
 #include <float.h>
 
@@ -263,24 +267,172 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve(BatchArgs a) {
     }
 }
 
+// The device-resident entry (simplex_solve_batch_device): every problem has the launch's one shape,
+// problem k is the work counter's value, A, b and c are read in place through element strides, and
+// the epilogue writes the caller's dense result arrays -- the solution scatter and the objective
+// row included -- so nothing is left for the host.  Between the build and the epilogue the steps
+// are k_batch_solve's, statement for statement (that kernel is left exactly as it was).
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    __shared__ double s_v[16];
+    __shared__ int s_i[16];
+    __shared__ double s_rv;
+    __shared__ int s_ri;
+    __shared__ unsigned s_k;
+    double *W;
+    if constexpr (LDS)
+        W = s_dyn;
+    else
+        W = a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m;
+    const BatchLay lay = sx_batch_lay(n, m);
+    BatchWork w;
+    w.T = W;
+    w.d = W + lay.d;
+    w.prow = W + lay.prow;
+    w.colE = W + lay.colE;
+    w.parts = reinterpret_cast<TilePart *>(W + lay.parts);
+    w.base = reinterpret_cast<int *>(W + lay.base);
+    w.n = n;
+    w.m = m;
+    w.ld = lay.ld;
+    const int ld = lay.ld, Ns = 1 + n + m, N1 = Ns + m;
+    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+    // consecutive lanes walk A's faster-varying dimension (uniform over the launch)
+    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    for (;;) {
+        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const unsigned k = s_k;
+        if (k >= (unsigned)a.count) return;
+        const double *A = a.A + (long long)k * a.A_sb, *bv = a.b + (long long)k * a.b_sb;
+        const double *cv = a.c + (long long)k * a.c_sb;
+
+        // orc_build_phase1, as k_batch_solve: the same copies and negations in either walk
+        if (by_col) {
+            for (int x = threadIdx.x; x < n * m; x += SX_TILE) {
+                const int i = x / n, j = x - i * n;
+                const double v = A[(long long)i * a.A_sr + (long long)j * a.A_sc];
+                w.T[(size_t)i * ld + 1 + j] = cmp_eps(bv[(long long)i * a.b_si], 0.0) < 0 ? -v : v;
+            }
+        } else {
+            for (int x = threadIdx.x; x < n * m; x += SX_TILE) {
+                const int j = x / m, i = x - j * m;
+                const double v = A[(long long)i * a.A_sr + (long long)j * a.A_sc];
+                w.T[(size_t)i * ld + 1 + j] = cmp_eps(bv[(long long)i * a.b_si], 0.0) < 0 ? -v : v;
+            }
+        }
+        for (int x = threadIdx.x; x < m * (m + 1); x += SX_TILE) {
+            const int i = x / (m + 1), t = x - i * (m + 1);
+            const double b = bv[(long long)i * a.b_si];
+            const double v = t == 0 ? b : (t - 1 == i ? 1.0 : 0.0);
+            w.T[(size_t)i * ld + (t == 0 ? 0 : n + t)] = cmp_eps(b, 0.0) < 0 ? -v : v;
+        }
+        for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j <= n + m ? 0.0 : 1.0;
+        for (int i = threadIdx.x; i < m; i += SX_TILE) w.base[i] = n + m + i;
+        __syncthreads();
+
+        long long p1 = 0, p2 = 0;
+        int status;
+        wg_update_objective(w, N1);
+        const int st1 = wg_solve(w, N1, a.max_pivots, budget, p1, s_v, s_i, &s_rv, &s_ri);
+        if (st1 == SX_PIVOT_CAP || st1 == SX_NUMERIC_FAIL || st1 == SX_EVICTED) {
+            status = st1;
+        } else if (cmp_eps(w.d[0], 0.0) < 0) {
+            status = SX_INFEASIBLE;
+        } else {
+            int art = 0;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) art |= w.base[i] >= n + m && w.base[i] < n + 2 * m;
+            status = __syncthreads_or(art) ? SX_DEGENERATE : SX_FEASIBLE;
+        }
+        // phase 2 entered: d then holds its row on [0, 1 + n + m) and stale phase-1 values behind it
+        const bool ph2 = status == SX_FEASIBLE;
+        if (ph2) {
+            // costs -c, slack costs 0, d[0] kept; canonicalise at width 1 + n + m and solve
+            for (int j = threadIdx.x; j < n; j += SX_TILE) w.d[1 + j] = -cv[(long long)j * a.c_sj];
+            for (int j = threadIdx.x; j < m; j += SX_TILE) w.d[1 + n + j] = 0.0;
+            __syncthreads();
+            wg_update_objective(w, Ns);
+            status = wg_solve(w, Ns, a.max_pivots, budget, p2, s_v, s_i, &s_rv, &s_ri);
+        }
+        // (every path above ends behind a barrier, so T, d and base are complete here)
+        const bool feasible = status == SX_FEASIBLE, evicted = status == SX_EVICTED;
+        if (a.x != nullptr) {
+            // getSolutionHost, staged in the pivot-row copy (1 + n + m >= n doubles, free by now):
+            // zeros, then x[base[i]] = T[i][0] for the basic variables, written out by consecutive lanes
+            for (int j = threadIdx.x; j < n; j += SX_TILE) w.prow[j] = 0.0;
+            __syncthreads();
+            if (feasible)
+                for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                    const unsigned bi = (unsigned)w.base[i];
+                    if (bi < (unsigned)n) w.prow[bi] = w.T[(size_t)i * ld];
+                }
+            __syncthreads();
+            double *x = a.x + (size_t)k * (size_t)n;
+            for (int j = threadIdx.x; j < n; j += SX_TILE) x[j] = w.prow[j];
+        }
+        if (a.base != nullptr) {
+            int *base_out = a.base + (size_t)k * (size_t)m;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = w.base[i];
+        }
+        // the row simplex_last_objective_row reports: phase 2's 1 + n + m entries once phase 2 was
+        // entered (what lies behind them in d is stale phase-1 data), else phase 1's full width;
+        // nothing of an evicted problem
+        const int width = evicted ? 0 : ph2 ? Ns : N1;
+        if (a.objrow != nullptr) {
+            double *row = a.objrow + (size_t)k * (size_t)N1;
+            for (int j = threadIdx.x; j < N1; j += SX_TILE) row[j] = j < width ? w.d[j] : 0.0;
+        }
+        if (threadIdx.x == 0) {
+            a.status[k] = evicted ? SX_NOT_ENDED : status;
+            a.pivots[2 * (size_t)k] = p1;
+            a.pivots[2 * (size_t)k + 1] = p2;
+            a.opt[k] = feasible ? w.d[0] : __builtin_nan("");
+            if (a.row_width != nullptr) a.row_width[k] = width;
+            if (evicted) atomicAdd(a.evicted, 1);
+        }
+        __syncthreads();  // the next problem overwrites the working set and s_k
+    }
+}
+
 }  // namespace
 
-int sx_batch_resident(bool lds, size_t lds_bytes) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        SX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_batch_solve<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SX_BATCH_LDS_BYTES));
-        attr_set = true;
+int sx_batch_resident(bool lds, size_t lds_bytes, bool dev) {
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[dev]) {
+        const void *fn = dev ? reinterpret_cast<const void *>(&k_batch_solve_dev<true>)
+                             : reinterpret_cast<const void *>(&k_batch_solve<true>);
+        SX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SX_BATCH_LDS_BYTES));
+        attr_set[dev] = true;
     }
-    int dev = 0, cus = 0, per_cu = 0;
-    SX_HIP(hipGetDevice(&dev));
-    SX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (lds)
+    int device = 0, cus = 0, per_cu = 0;
+    SX_HIP(hipGetDevice(&device));
+    SX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (dev) {
+        if (lds)
+            SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve_dev<true>, SX_TILE, lds_bytes));
+        else
+            SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve_dev<false>, SX_TILE, 0));
+    } else if (lds) {
         SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve<true>, SX_TILE, lds_bytes));
-    else
+    } else {
         SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve<false>, SX_TILE, 0));
+    }
     if (per_cu < 1) SX_FATAL("the batch kernel does not fit a compute unit");
     return per_cu * cus;
+}
+
+void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    if (grid < 1 || a.count < 1) return;
+    if (lds) {
+        if (lds_bytes > SX_BATCH_LDS_BYTES) SX_FATAL("batch kernel: working set exceeds the LDS class");
+        k_batch_solve_dev<true><<<grid, SX_TILE, lds_bytes, s>>>(a);
+    } else {
+        if (a.ws == nullptr || a.slice < 1) SX_FATAL("batch kernel: no workspace");
+        k_batch_solve_dev<false><<<grid, SX_TILE, 0, s>>>(a);
+    }
+    SX_HIP(hipGetLastError());
 }
 
 void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s) {

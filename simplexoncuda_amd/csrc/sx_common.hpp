@@ -377,6 +377,37 @@ struct BatchArgs {
     long long max_pivots;  // per phase, < 0: none (status SX_PIVOT_CAP)
     long long budget;      // resident pivots per phase, 0: sx_batch_default_budget
 };
-// workgroups of the batch kernel the current device holds at once with this much dynamic LDS
-int sx_batch_resident(bool lds, size_t lds_bytes);
+// The device-resident entry (simplex_solve_batch_device): `count` problems of one shape read in
+// place from strided device arrays (element strides: batch, constraint row, variable column), every
+// result written to dense device arrays by the kernel's epilogue.  Problem k of the launch is the
+// work counter's value; there are no per-problem records.
+struct BatchDevArgs {
+    int n, m, count;
+    const double *A;
+    long long A_sb, A_sr, A_sc;
+    const double *b;
+    long long b_sb, b_si;
+    const double *c;
+    long long c_sb, c_sj;
+    long long max_pivots;  // per phase, < 0: none (status SX_PIVOT_CAP)
+    long long budget;      // resident pivots per phase, 0: sx_batch_default_budget
+    int *status;           // [count]; an evicted problem gets SX_NOT_ENDED
+    long long *pivots;     // [count][2]
+    double *opt;           // [count]: d[0] when FEASIBLE, else a quiet NaN
+    double *x;             // [count][n] or null: getSolutionHost when FEASIBLE, else +0.0
+    int *base;             // [count][m] or null
+    double *objrow;        // [count][1 + n + 2m] or null: the final objective row, zero-padded
+    int *row_width;        // [count] or null: 1 + n + m after phase 2, 1 + n + 2m after phase 1, 0 evicted
+    int *evicted;          // [1] problems left SX_NOT_ENDED (zero at launch)
+    unsigned *counter;     // the launch's work counter (zero at launch)
+    double *ws;            // workspace-resident: the slices; null for the LDS class
+    long long slice;       // doubles per slice
+};
+// Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
+#define SX_BATCH_DEV_HEADER 256
+
+// workgroups of the batch kernel (dev: of the device-resident entry's kernel) the current device
+// holds at once with this much dynamic LDS
+int sx_batch_resident(bool lds, size_t lds_bytes, bool dev = false);
 void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s);

@@ -2399,6 +2399,81 @@ int simplex_solve_batch(problem_t *const *problems, int count, long long max_piv
     return 0;
 }
 
+// The device-resident entry: uniform shape, device pointers in and out, the caller's stream and
+// workspace.  Nothing here allocates, copies or synchronises, and none of the state above (g_bb,
+// g_batch_mu, g_batch_counts) is touched: two memsets and one launch are enqueued.
+// workspace: [SX_BATCH_DEV_HEADER bytes: the work counter] [class 1: one slice per workgroup]
+static int batch_device_grid(int n, int m, int count, int cls) {
+    const size_t set = (size_t)sx_batch_lay(n, m).total * sizeof(double);
+    if (cls == 2) return std::min(count, sx_batch_resident(true, set, true));
+    const long long fit = (long long)std::max<size_t>(1, SX_BATCH_WS_BYTES / set);
+    return (int)std::min<long long>(std::min(count, sx_batch_resident(false, 0, true)), fit);
+}
+
+long long simplex_batch_device_workspace(int n, int m, int count) {
+    if (count < 0) return -1;
+    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
+    if (cls == 0) return -3;
+    if (cls == 2 || count == 0) return SX_BATCH_DEV_HEADER;
+    return SX_BATCH_DEV_HEADER +
+           (long long)batch_device_grid(n, m, count, cls) * sx_batch_lay(n, m).total * (long long)sizeof(double);
+}
+
+int simplex_solve_batch_device(const simplex_batch_device_t *args) {
+    if (args == nullptr || args->count < 0) return -1;
+    const int n = args->n, m = args->m, count = args->count;
+    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
+    if (cls == 0) return -3;
+    if (count == 0) return 0;
+    if (args->A == nullptr || args->b == nullptr || args->c == nullptr || args->status == nullptr ||
+        args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr)
+        return -2;
+    // a stride of 0 would alias the elements of a dimension that has more than one
+    if ((count > 1 && (args->A_sb == 0 || args->b_sb == 0 || args->c_sb == 0)) ||
+        (m > 1 && (args->A_sr == 0 || args->b_si == 0)) || (n > 1 && (args->A_sc == 0 || args->c_sj == 0)))
+        return -4;
+    if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0) return -5;
+    const int grid = batch_device_grid(n, m, count, cls);
+    const long long set = sx_batch_lay(n, m).total;
+    const long long need = SX_BATCH_DEV_HEADER + (cls == 1 ? (long long)grid * set * (long long)sizeof(double) : 0);
+    if (args->workspace_bytes < need) return -5;
+
+    BatchDevArgs a{};
+    a.n = n;
+    a.m = m;
+    a.count = count;
+    a.A = args->A;
+    a.A_sb = args->A_sb;
+    a.A_sr = args->A_sr;
+    a.A_sc = args->A_sc;
+    a.b = args->b;
+    a.b_sb = args->b_sb;
+    a.b_si = args->b_si;
+    a.c = args->c;
+    a.c_sb = args->c_sb;
+    a.c_sj = args->c_sj;
+    a.max_pivots = args->max_pivots;
+    a.budget = g_batch_budget;
+    a.status = args->status;
+    a.pivots = args->pivots;
+    a.opt = args->opt;
+    a.x = args->x;
+    a.base = args->base;
+    a.objrow = args->objrow;
+    a.row_width = args->row_width;
+    a.evicted = args->evicted;
+    a.counter = static_cast<unsigned *>(args->workspace);
+    if (cls == 1) {
+        a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
+        a.slice = set;
+    }
+    hipStream_t s = static_cast<hipStream_t>(args->stream);
+    SX_HIP(hipMemsetAsync(args->workspace, 0, SX_BATCH_DEV_HEADER, s));
+    SX_HIP(hipMemsetAsync(args->evicted, 0, sizeof(int), s));
+    sx_launch_batch_solve_dev(cls == 2, a, grid, (size_t)set * sizeof(double), s);
+    return 0;
+}
+
 // ---------------------------------------------------------------- tabular_t API
 // tabular.cu:25-39.  The caller fills the tableau itself, so every one of its 1+n+2m columns is
 // stored (no artificial-column aliasing: the caller's artificial columns need not equal the
