@@ -167,3 +167,142 @@ def test_explain_divergence_names_the_pivot(side, word):
     msg = tl.explain_divergence(T0, d0, base0, k, got[2], got[4], run_once)
     assert calls == [wrong_at + 1]  # (one extra device run, with the diverging count)
     assert msg.startswith("first diverging pivot: %d (0-based)" % wrong_at) and word in msg and "eps" in msg
+
+
+# ------------------------------------------------------------------ whole LPs for the batch kernels
+_BATCH = {}
+
+
+def _batch(name):
+    """(A, b, c), the census over both phases and the oracle's result with its objective row of a
+    BATCH_CASES case: computed once, never written"""
+    if name not in _BATCH:
+        A, b, c = tl.make_batch(name)
+        ref = oracle.two_phase(A, b, c)
+        ref["row"] = oracle.last_objective_row().copy()
+        _BATCH[name] = ((A, b, c), tl.census_two_phase(A, b, c), ref)
+    return _BATCH[name]
+
+
+@pytest.mark.parametrize("name", list(tl.BATCH_CASES))
+def test_batch_case_floors(name):
+    """the whole-LP ladders of test_gpu_batch_ladders.py: the oracle ends FEASIBLE after the stated
+    pivots, and in each phase the tree order (B-small: the lanes; the others: the merge of the tile
+    winners) decides at least the floor of pivots"""
+    gen, (n, m, g), kw, seed, cls, pivots = tl.BATCH_CASES[name]
+    (A, b, c), cen, ref = _batch(name)
+    print(name, cen)
+    assert A.shape == (m, n) and b.shape == (m,) and c.shape == (n,)
+    assert (ref["status"], ref["pivots"]) == (oracle.FEASIBLE, pivots) and cen["pivots"] == pivots
+    assert len(ref["row"]) == 1 + n + m
+    for (phase, key), floor in tl.BATCH_FLOORS[name].items():
+        assert cen[phase][key] >= floor, (phase, key)
+    if name == "O-small":
+        A0, b0, _ = tl.make(name)
+        assert np.array_equal(A, A0) and np.array_equal(b, b0) and tl.WHOLE_SOLVES[name] == (oracle.FEASIBLE, pivots)
+
+
+def test_batch_case_shapes():
+    """what each case is sized for: candidates per side in 512-wide tiles, sub-eps trims"""
+    shape = {name: tl.BATCH_CASES[name][1][:2] for name in tl.BATCH_CASES}
+    n, m = shape["B-small"]
+    assert n + 2 * m <= 512  # (one tile on each side in both phases)
+    n, m = shape["B-wide3"]
+    assert 1024 < n + m and n + 2 * m <= 1536  # (3 entering tiles in both phases)
+    n, m = shape["B-w1024"]
+    assert n + 2 * m == 1024
+    n, m = shape["B-w1025"]
+    assert n + 2 * m == 1025
+    n, m = shape["B-w65t"]
+    assert n + 2 * m == 64 * 512 + 1 and (n + m + 511) // 512 == 64
+    n, m = shape["B-ws"]
+    assert 512 < m <= 1024 and 1024 < n + 2 * m <= 1536  # (2 ratio tiles, 3 entering tiles in phase 1)
+    n, m = shape["B-trim"]
+    assert 512 < m <= 1024
+    A = tl.make_batch("B-trim")[0]
+    assert np.count_nonzero((A > 0) & (A < 1e-9)) > 0
+
+
+# (ii) merges tile winners, so it is held against the cases with a tile-merge floor; O-small and
+# B-small decide inside one tile's lanes (tile_merge_census: 0 on both sides), which (i) covers
+_STANDINS = [(name, sel) for name in tl.BATCH_CASES for sel in (tl.select_np, tl.select_tiles_rev)
+             if sel is tl.select_np or any(key.endswith("_rev") for _, key in tl.BATCH_FLOORS[name])]
+
+
+@pytest.mark.parametrize("name,select", _STANDINS, ids=["%s-%s" % (n, s.__name__) for n, s in _STANDINS])
+def test_batch_cases_tell_standins_apart(name, select):
+    """a whole two-phase solve with another selection rule on both sides -- (i) np.argmin, (ii) the
+    reference's tree inside each 512-wide tile with the tile winners merged right to left -- differs
+    from the oracle in a field the GPU tests compare (on B-trim only in the bits of the objective
+    row and of the objective), so a batch kernel with that rule cannot pass them"""
+    (A, b, c), _, ref = _batch(name)
+    got = tl.standin_two_phase(A, b, c, select)
+    assert not tl.same_result(got, ref)
+    if name == "B-trim":
+        assert got["pivots"] == ref["pivots"] and np.array_equal(got["base"], ref["base"])
+    elif name in ("B-wide3", "B-w1024", "B-w1025", "B-w65t", "B-ws") or select is tl.select_np:
+        assert not np.array_equal(got["base"], ref["base"])
+
+
+def test_standin_with_the_reference_rule_is_the_oracle():
+    """the stand-in replay itself is exact: with the oracle's own argmin it returns the oracle's
+    result, whole and capped (so a difference above is the selection rule's)"""
+    (A, b, c), _, ref = _batch("B-small")
+    def rule(v):
+        return oracle.argmin(v)[0]
+    assert tl.same_result(tl.standin_two_phase(A, b, c, rule), ref)
+    for cap in (0, 7, 133, 134, 150):
+        want = oracle.two_phase(A, b, c, cap)
+        want["row"] = oracle.last_objective_row().copy()
+        assert tl.same_result(tl.standin_two_phase(A, b, c, rule, cap), want), cap
+
+
+@pytest.mark.parametrize("where", ["below", "at", "above"])
+def test_boundary_lps_oracle(where):
+    """compare()'s eligibility boundaries as whole LPs: phase 1 is m slack pivots that leave the
+    tableau as built, and phase 2's first decision is the boundary one"""
+    x = tl.BOUNDARY[where]
+    for kind in ("entry", "cost"):
+        A, b, c = tl.boundary_lp(kind, x)
+        m, n = A.shape
+        assert (m, n) == (20, 6) and np.all(b > 0) and np.all(b == np.round(b)) and np.all(A.sum(axis=0) < 1)
+        T, d, base = tl.phase1_state(A, b)
+        T0 = T.copy()
+        assert oracle.solve(T, d, base) == (oracle.FEASIBLE, m) and np.array_equal(T, T0)
+        assert np.array_equal(base, n + np.arange(m))
+    A, b, c = tl.boundary_lp("entry", x)
+    assert int(np.argmax(c)) == 3 and A[:, 3].max() == x and np.sort(A[:, 3])[-2] == 0.5e-9
+    assert np.signbit(A[7, 3]) and A[7, 3] == 0 and A[15, 3] == tl.BOUNDARY["below"] / 2
+    ref = oracle.two_phase(A, b, c)
+    if where == "below":
+        assert (ref["status"], ref["pivots"]) == (oracle.UNBOUNDED, (20, 0))
+    else:
+        assert ref["pivots"][0] == 20 and ref["pivots"][1] >= 1 and ref["base"][11] == 3
+    A, b, c = tl.boundary_lp("cost", x)
+    assert c[4] == x and np.count_nonzero(c > 0) == 1
+    ref = oracle.two_phase(A, b, c)
+    assert ref["status"] == oracle.FEASIBLE
+    assert ref["pivots"] == ((20, 0) if where == "below" else (20, 1))
+    assert (4 in ref["base"]) == (where != "below")
+
+
+@pytest.mark.parametrize("name,select,word", [("B-small", tl.select_np, "ENTERS"), ("B-ws", tl.select_tiles_rev, "LEAVING")])
+def test_explain_batch_divergence_names_the_pivot(name, select, word):
+    """explain_batch_divergence on a stand-in device: it names a pivot count k at which the stand-in's
+    rule really picks differently on the oracle's state after k - 1 pivots, within about 12 runs"""
+    (A, b, c), _, ref = _batch(name)
+    calls = []
+
+    def run(k):
+        calls.append(k)
+        got = tl.standin_two_phase(A, b, c, select, max_pivots=k)
+        return got["status"], got["pivots"], got["base"]
+
+    msg = tl.explain_batch_divergence(A, b, c, run)
+    assert len(calls) <= 13 and all(0 < k <= ref["pivots"][0] for k in calls)
+    assert msg.startswith("first differing basis: after %d pivots of phase 1" % calls[-1]) and word in msg and "eps" in msg
+    T, d, base = tl.phase1_state(A, b)
+    assert oracle.solve(T, d, base, max_pivots=calls[-1] - 1)[1] == calls[-1] - 1
+    e = oracle.argmin(d[1:])[0]
+    r = oracle.argmin(tl.ratios(T, e))[0]
+    assert (select(d[1:]), select(tl.ratios(T, e))) != (e, r)

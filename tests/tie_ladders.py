@@ -41,6 +41,36 @@ another index than the reference's pass 2; entering | ratio):
 40 entering-sensitive pivots are exact ties between slack columns at -1.0, where the tree picks
 among equal values.)  Whole solves of D-1 and O-small with the
 ladder cost vector `cost_vector`: see WHOLE_SOLVES below.
+
+Whole LPs for the batched-solve kernels (BATCH_CASES: sized for the LDS and the workspace class of
+sx_batch.hip, cost vector cost_vector(n, seed); tests/test_gpu_batch_ladders.py runs them through
+both batch entries).  census_two_phase, per phase (k = the oracle's pivots of the phase, all of
+them replayed), the columns of the two tables above:
+
+    case     generator(n, m, g) seed          phase    k  sens       argmin     scan       win        lin/rev enter | ratio
+    B-small  overlap(40, 60, 8, spare=8) 1        1  133   23 /  13   20 /  12   22 /   5   11 /  16  0/0   | 0/0
+                                                  2   57    9 /   5    6 /   5    7 /   3   11 /   5  0/0   | 0/0
+    B-wide3  wide(1100, 12, 3, spare=4) 2         1   13   10 /   1   10 /   1    6 /   1    9 /   2  0/9   | 0/0
+                                                  2   15   10 /   1    9 /   1    4 /   0   10 /   3  0/7   | 0/0
+    B-w1024  wide(1000, 12, 3, spare=4) 2         1   12    8 /   1    8 /   1    5 /   1    8 /   2  0/8   | 0/0
+                                                  2   14    8 /   1    8 /   0    5 /   1   10 /   3  0/6   | 0/0
+    B-w1025  wide(1001, 12, 3, spare=4) 1         1   12   10 /   2    9 /   1    9 /   2    8 /   2  0/8   | 0/0
+                                                  2   15   10 /   1    8 /   1    6 /   0   12 /   3  0/7   | 0/0
+    B-ws     overlap(40, 600, 12) 1               1  880  550 / 156  543 / 137  520 /  87  168 / 211  0/455 | 0/100
+                                                  2   41   26 /  11   24 /  11   19 /   6   31 /  14  0/26  | 0/11
+    B-trim   disjoint(20, 560, 24) 1              1  560  518 /  17  518 /  16  516 /  10   18 /  20  0/472 | 0/14
+                                                  2   20   16 /   0   13 /   0   13 /   0   19 /   0  0/0   | 0/0
+    O-small  overlap(40, 333, 16) 1               1  670  250 /  43  244 /  34  246 /  27   31 /  51  0/0   | 0/0
+                                                  2   73   10 /  18    8 /  14    8 /  10   15 /  26  0/0   | 0/0
+    B-w65t   wide(32745, 12, 3, spare=4) 1        1   13   11 /   1   10 /   1    9 /   1    9 /   1  0/9   | 0/0
+                                                  2   14    8 /   2    6 /   1    4 /   1    9 /   3  0/6   | 0/0
+
+Whole solves with another selection rule (standin_two_phase): np.argmin ends at another basis on
+every case but B-trim; the tile winners merged right to left end at another basis on B-wide3,
+B-w1024, B-w1025, B-w65t and B-ws and change nothing on B-small and O-small (no pivot of theirs is decided
+between tiles).  On B-trim both rules end at the oracle's basis after the oracle's pivot counts, with
+other bits in the objective and the objective row -- and at another basis mid-solve (after 1 and 3
+pivots), which is what the capped prefixes of the GPU tests see.
 """
 import numpy as np
 
@@ -135,6 +165,43 @@ def make(name):
     return A, b, k
 
 
+# Whole LPs for the resident workgroups of the batched solve (sx_batch.hip wg_argmin): name ->
+# (generator, (n, m, g), generator keywords, seed, batch class (2 LDS, 1 workspace), the oracle's
+# (phase-1, phase-2) pivots).  The cost vector is cost_vector(n, seed); every solve ends FEASIBLE.
+BATCH_CASES = {
+    "B-small": ("overlap", (40, 60, 8), {"spare": 8}, 1, 2, (133, 57)),   # one tile each side: the lane tree
+    "B-wide3": ("wide", (1100, 12, 3), {"spare": 4}, 2, 2, (13, 15)),     # 3 entering tiles in both phases, in LDS
+    "B-w1024": ("wide", (1000, 12, 3), {"spare": 4}, 2, 2, (12, 14)),     # n + 2m = 1024: exactly 2 full tiles
+    "B-w1025": ("wide", (1001, 12, 3), {"spare": 4}, 1, 2, (12, 15)),     # n + 2m = 1025: the third tile holds one value
+    "B-ws": ("overlap", (40, 600, 12), {}, 1, 1, (880, 41)),              # ratio over 2 row tiles, entering over 3
+    "B-trim": ("disjoint", (20, 560, 24), {}, 1, 1, (560, 20)),           # sub-eps trims, ratio over 2 tiles
+    "O-small": ("overlap", (40, 333, 16), {}, 1, 1, (670, 73)),           # (CASES["O-small"], WHOLE_SOLVES)
+    # n + 2m = 32769: 65 entering tiles (64 in phase 2), so pass 2 combines winners across its 32-lane halves and waves
+    "B-w65t": ("wide", (32769 - 24, 12, 3), {"spare": 4}, 1, 1, (13, 14)),
+}
+
+# Floors of census_two_phase per case: {(phase, key): floor}, conditions on the inputs like CASES'.
+BATCH_FLOORS = {
+    "B-small": {(1, "enter_sensitive"): 15, (1, "ratio_sensitive"): 10, (2, "enter_sensitive"): 5, (2, "ratio_sensitive"): 3},
+    "B-wide3": {(1, "enter_rev"): 6, (2, "enter_rev"): 4},
+    "B-w1024": {(1, "enter_rev"): 5, (2, "enter_rev"): 4},
+    "B-w1025": {(1, "enter_rev"): 5, (2, "enter_rev"): 4},
+    "B-ws": {(1, "ratio_rev"): 60, (2, "ratio_rev"): 6, (1, "enter_rev"): 300, (2, "enter_rev"): 15},
+    "B-trim": {(1, "enter_sensitive"): 400, (1, "ratio_rev"): 10},
+    "O-small": {},
+    "B-w65t": {(1, "enter_rev"): 5, (2, "enter_rev"): 4},
+}
+
+
+def make_batch(name, seed=None):
+    """(A, b, c) of a BATCH_CASES case; `seed` other than the committed one: a neighbour of the
+    same shape (the floors are measured on the committed seed only)"""
+    gen, args, kw, seed0, _, _ = BATCH_CASES[name]
+    seed = seed0 if seed is None else seed
+    A, b = GENERATORS[gen](*args, seed, **kw)
+    return A, b, cost_vector(args[0], seed)
+
+
 def phase1_state(A, b):
     """the canonical phase-1 tableau (T, d, base) of (A, b)"""
     T, d, base = oracle.build_phase1(A, b)
@@ -189,6 +256,33 @@ def boundary_state(kind, x):
     return T, d, base
 
 
+def boundary_lp(kind, x):
+    """The same boundaries as a whole LP (A 20 x 6, b, c) for the batch entries, which take no
+    tableau.  b: positive integers; A: multiples of 1/128 with every column sum below 1, so phase 1
+    is exactly m slack pivots (each on a 1.0, every other entry of the column 0) that leave
+    [b | A | I] as built, and phase 2's first decision falls on the raw data.
+    kind "entry": the column of the largest cost (column 3) has x in row 11 and otherwise entries
+    <= 0.5e-9.  The oracle: UNBOUNDED after (20, 0) pivots for x < 1e-9, else phase 2 pivots.
+    kind "cost": the only positive cost is x (column 4).  The oracle: FEASIBLE after (20, 0) pivots
+    for x < 1e-9, else (20, 1) with column 4 basic."""
+    m, n = 20, 6
+    rng = np.random.default_rng(20)
+    b = rng.integers(1, 9, size=m).astype(np.float64)
+    A = rng.integers(0, 6, size=(m, n)) / 128.0
+    c = -(1.0 + rng.integers(0, 4, size=n).astype(np.float64))
+    if kind == "entry":
+        c[3], c[1] = 2.0, 1.0
+        col = -rng.integers(0, 4, size=m) / 128.0
+        col[2], col[7], col[15] = 0.5e-9, -0.0, BOUNDARY["below"] / 2
+        col[11] = x
+        A[:, 3] = col
+    else:
+        assert kind == "cost"
+        A[:, 4] = rng.integers(1, 6, size=m) / 128.0
+        c[4] = x
+    return A, b, c
+
+
 # ------------------------------------------------------------------ the plain rules
 def ratios(T, e):
     """createIndicatorsVector: b_i / a_ie where a_ie >= 1e-9, else DBL_MAX"""
@@ -198,6 +292,11 @@ def ratios(T, e):
     with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
         out[ok] = T[ok, 0] / col[ok]
     return out
+
+
+def _negative(x):
+    """compare(x, 0) < 0"""
+    return bool(x < 0 and not abs(x) < EPS)
 
 
 def eps_scan(v):
@@ -218,6 +317,41 @@ def window(v, i, width=EPS):
         return np.flatnonzero((np.abs(v - v[i]) < width) & (v != v[i]))
 
 
+_CENSUS_KEYS = ("enter_argmin", "enter_scan", "enter_sensitive", "enter_window",
+                "ratio_argmin", "ratio_scan", "ratio_sensitive", "ratio_window")
+_MERGE_KEYS = ("enter_lin", "enter_rev", "ratio_lin", "ratio_rev")
+
+
+def _replay(T, d, base, k, count):
+    """up to k pivots (k < 0: until the phase ends) of the state (T, d, base), in place, with
+    oracle.pivot; before each pivot is applied, count(v, e, rv, r) sees the entering vector d[1:],
+    the oracle's entering index, the ratio vector of that column and the oracle's leaving row.
+    Returns (pivots taken, the status that ended the replay)."""
+    done = 0
+    while k < 0 or done < k:
+        v = d[1:].copy()
+        e_pred = oracle.argmin(v)[0]
+        rv = ratios(T, e_pred) if e_pred >= 0 else None
+        st, e, r = oracle.pivot(T, d, base)
+        if st != oracle.NOT_ENDED:
+            return done, st
+        assert e == e_pred and r == oracle.argmin(rv)[0]
+        done += 1
+        count(v, e, rv, r)
+    return done, oracle.PIVOT_CAP
+
+
+def _count_census(out):
+    def count(v, e, rv, r):
+        for side, vec, win in (("enter", v, e), ("ratio", rv, r)):
+            a, s = int(np.argmin(vec)) != win, eps_scan(vec) != win
+            out[side + "_argmin"] += a
+            out[side + "_scan"] += s
+            out[side + "_sensitive"] += a or s
+            out[side + "_window"] += window(vec, win).size > 0
+    return count
+
+
 def census(A, b, k):
     """Replay k pivots of (A, b)'s phase 1 with oracle.pivot and count the pivots the combine tree
     decides.  Per side (entering: d[1:]; ratio: the ratio vector of the entering column):
@@ -225,23 +359,8 @@ def census(A, b, k):
     `*_sensitive`: from either; `*_window`: the winner has a second, different value inside its
     eps-window.  `done`: pivots taken (k unless the phase ended)."""
     T, d, base = phase1_state(A, b)
-    out = {"done": 0, "enter_argmin": 0, "enter_scan": 0, "enter_sensitive": 0, "enter_window": 0,
-           "ratio_argmin": 0, "ratio_scan": 0, "ratio_sensitive": 0, "ratio_window": 0}
-    for _ in range(k):
-        v = d[1:].copy()
-        e_pred = oracle.argmin(v)[0]
-        rv = ratios(T, e_pred) if e_pred >= 0 else None
-        st, e, r = oracle.pivot(T, d, base)
-        if st != oracle.NOT_ENDED:
-            break
-        assert e == e_pred and r == oracle.argmin(rv)[0]
-        out["done"] += 1
-        for side, vec, win in (("enter", v, e), ("ratio", rv, r)):
-            a, s = int(np.argmin(vec)) != win, eps_scan(vec) != win
-            out[side + "_argmin"] += a
-            out[side + "_scan"] += s
-            out[side + "_sensitive"] += a or s
-            out[side + "_window"] += window(vec, win).size > 0
+    out = dict.fromkeys(("done",) + _CENSUS_KEYS, 0)
+    out["done"] = _replay(T, d, base, k, _count_census(out))[0]
     return out
 
 
@@ -258,25 +377,122 @@ def _tile_merges(v):
     return oracle.argmin_pass2(pv, pi)[0], int(pi[eps_scan(pv)]), int(pi[rev])
 
 
+def _count_merges(out):
+    def count(v, e, rv, r):
+        for side, vec, win in (("enter", v, e), ("ratio", rv, r)):
+            ref, lin, rev = _tile_merges(vec)
+            assert ref == win  # (tiles + pass 2 = the whole argmin below 1024 tiles)
+            out[side + "_lin"] += lin != ref
+            out[side + "_rev"] += rev != ref
+    return count
+
+
 def tile_merge_census(A, b, k):
     """Pivots (of k) at which merging the tile winners in another order than the reference's pass 2
     picks another index -- what a tile hand-off that combined records linearly, or ranks in another
     order, would get wrong: `*_lin` left to right, `*_rev` right to left; entering / ratio side."""
     T, d, base = phase1_state(A, b)
-    out = {"done": 0, "enter_lin": 0, "enter_rev": 0, "ratio_lin": 0, "ratio_rev": 0}
-    for _ in range(k):
-        v = d[1:].copy()
-        e = oracle.argmin(v)[0]
-        rv = ratios(T, e) if e >= 0 else None
-        if oracle.pivot(T, d, base)[0] != oracle.NOT_ENDED:
-            break
-        out["done"] += 1
-        for side, vec in (("enter", v), ("ratio", rv)):
-            ref, lin, rev = _tile_merges(vec)
-            assert ref == oracle.argmin(vec)[0]  # (tiles + pass 2 = the whole argmin below 1024 tiles)
-            out[side + "_lin"] += lin != ref
-            out[side + "_rev"] += rev != ref
+    out = dict.fromkeys(("done",) + _MERGE_KEYS, 0)
+    out["done"] = _replay(T, d, base, k, _count_merges(out))[0]
     return out
+
+
+def phase2_state(T, d, base, c):
+    """phase 2's canonical state as the batch kernels (and orc_two_phase) set it up from phase 1's
+    final one: the artificial columns leave d, d[1 : 1+n] = -c, the slack costs are zeroed, d[0] is
+    kept, then update_objective at width 1 + n + m.  T is shared, d is new."""
+    m, n = T.shape[0], len(c)
+    d2 = d[:1 + n + m].copy()
+    d2[1:1 + n] = -np.asarray(c, dtype=np.float64)
+    d2[1 + n:] = 0.0
+    oracle.update_objective(T, d2, base)
+    return T, d2, base
+
+
+def census_two_phase(A, b, c):
+    """`census` and `tile_merge_census` over both phases of the whole solve of (A, b, c), which has
+    to end FEASIBLE: {1: counts of phase 1, 2: counts of phase 2, "pivots": (p1, p2)}.  The replay's
+    pivot counts and final basis are asserted equal to oracle.two_phase's."""
+    ref = oracle.two_phase(A, b, c)
+    assert ref["status"] == oracle.FEASIBLE
+    m, n = A.shape
+    out = {}
+    T, d, base = phase1_state(A, b)
+    for phase in (1, 2):
+        cnt = dict.fromkeys(("done",) + _CENSUS_KEYS + _MERGE_KEYS, 0)
+        a, t = _count_census(cnt), _count_merges(cnt)
+        cnt["done"], st = _replay(T, d, base, -1, lambda *x: (a(*x), t(*x)))
+        assert st == oracle.FEASIBLE
+        out[phase] = cnt
+        if phase == 1:
+            assert not _negative(d[0]) and not np.any(base >= n + m)  # (phase 1 ended FEASIBLE)
+            T, d, base = phase2_state(T, d, base, c)
+    out["pivots"] = (out[1]["done"], out[2]["done"])
+    assert out["pivots"] == ref["pivots"] and np.array_equal(base, ref["base"])
+    return out
+
+
+# ------------------------------------------------------------------ stand-in solvers
+def select_np(vec):
+    """a selection rule that is not the reference's: the plain minimum"""
+    return int(np.argmin(vec))
+
+
+def select_tiles_rev(vec):
+    """a selection rule that is not the reference's: its tree inside every 512-wide tile, the tile
+    winners merged right to left (more than 512 candidates only; below, the reference's rule)"""
+    return _tile_merges(vec)[2] if len(vec) > 512 else oracle.argmin(vec)[0]
+
+
+def _standin_solve(T, d, base, select, max_pivots):
+    """orc_solve with `select` in place of the eps-argmin tree on both sides"""
+    k = 0
+    while True:
+        if 0 <= max_pivots <= k:
+            return oracle.PIVOT_CAP, k
+        e = select(d[1:])
+        dmin = d[1 + e]
+        if not _negative(dmin):
+            return oracle.FEASIBLE, k
+        if not np.any(T[:, 1 + e] >= EPS):
+            return oracle.UNBOUNDED, k
+        r = select(ratios(T, e))
+        base[r] = e
+        prow, colE = T[r, :len(d)].copy(), T[:, 1 + e].copy()
+        oracle.apply_update(T, d, prow, colE, r, prow[1 + e], dmin)
+        k += 1
+
+
+def standin_two_phase(A, b, c, select, max_pivots=-1):
+    """orc_two_phase with `select` as the selection rule: what a batch kernel with that rule in
+    place of wg_argmin's tree would return -- oracle.two_phase's fields plus the objective "row" """
+    m, n = A.shape
+    T, d, base = phase1_state(A, b)
+    st, p1 = _standin_solve(T, d, base, select, max_pivots)
+    p2 = 0
+    if st != oracle.PIVOT_CAP:
+        st = oracle.INFEASIBLE if _negative(d[0]) else \
+            oracle.DEGENERATE if np.any((base >= n + m) & (base < n + 2 * m)) else oracle.FEASIBLE
+    if st == oracle.FEASIBLE:
+        T, d, base = phase2_state(T, d, base, c)
+        st, p2 = _standin_solve(T, d, base, select, max_pivots)
+    x, opt = np.zeros(n), 0.0
+    if st == oracle.FEASIBLE:
+        opt = float(d[0])
+        x[base[base < n]] = T[base < n, 0]
+    return {"status": st, "x": x, "opt": opt, "base": base, "pivots": (p1, p2), "row": d}
+
+
+def same_result(got, ref):
+    """every field the GPU tests compare (tests/batch_refs.py same_as_refs), as one boolean"""
+    def bits(a):
+        return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+    if got["status"] != ref["status"] or got["pivots"] != ref["pivots"] or not np.array_equal(got["base"], ref["base"]):
+        return False
+    if ref["status"] == oracle.FEASIBLE and not (np.array_equal(bits(got["opt"]), bits(ref["opt"]))
+                                                 and np.array_equal(bits(got["x"]), bits(ref["x"]))):
+        return False
+    return len(got["row"]) == len(ref["row"]) and np.array_equal(bits(got["row"]), bits(ref["row"]))
 
 
 # ------------------------------------------------------------------ first diverging pivot
@@ -403,3 +619,77 @@ def explain_divergence(T0, d0, base0, k, got_base, got_done, run_device):
             e_dev, r_dev, _window_text(d[1:], e, e_dev))
     return msg + "the device's LEAVING row is %d instead (entering %d agrees); ratios around the oracle's winner: %s" % (
         r_dev, e, _window_text(ratios(T, e), r, r_dev))
+
+
+# ------------------------------------------------------------------ first diverging pivot of a whole solve
+def _first_bad(lo, hi, bad):
+    """the smallest k in (lo, hi] with bad(k), given not bad(lo) and bad(hi): bisection"""
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if bad(mid):
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def explain_batch_divergence(A, b, c, run_device):
+    """The text of a failed whole-solve comparison of a batch entry: the first pivot count at which
+    the device's basis is not the oracle's.  The batch entries take whole LPs only, so the device is
+    probed through its pivot cap: `run_device(k)` -> (status, (p1, p2), base) of the solve with
+    max_pivots = k.  A cap k <= p1 (the oracle's phase-1 count) stops in phase 1 after k pivots; a
+    cap k > p1 lets phase 1 end and stops phase 2 after k pivots, so of phase 2 only the counts
+    above p1 can be probed.  Bisection over phase 1, then over phase 2: about log2(p1) + log2(p2)
+    device runs.  The eps-window around the oracle's winner at that pivot is printed."""
+    m, n = A.shape
+    T0, d0, base0 = phase1_state(A, b)
+    piv1, bases1, st1, (T1, d1, base1) = oracle_trace(T0, d0, base0, 1 << 40)
+    p1 = len(piv1)
+    runs = []
+
+    def bad(phase, bases):
+        def f(k):
+            st, piv, base = run_device(k)
+            runs.append(k)
+            want = (k, 0) if phase == 1 else (p1, k)
+            return tuple(piv) != want or not np.array_equal(base, bases[k])
+        return f
+
+    def report(phase, k, T, d, base, piv, bases):
+        # (T, d, base): the phase's initial state; the pivot that takes the count to k is piv[k - 1]
+        st, pv, got = run_device(k)
+        for _ in range(k - 1):
+            oracle.pivot(T, d, base)
+        e, r = piv[k - 1]
+        msg = "first differing basis: after %d pivots of phase %d (device: status %d, pivots %r), where the oracle " \
+            "enters %d and row %d leaves; " % (k, phase, st, tuple(pv), e, r)
+        diff = np.flatnonzero(got != bases[k - 1])
+        if diff.size != 1:
+            return msg + "the device's basis differs from the oracle's basis after %d pivots in rows %s" % (
+                k - 1, diff[:8].tolist())
+        r_dev, e_dev = int(diff[0]), int(got[diff[0]])
+        if e_dev != e:
+            return msg + "the device ENTERS %d instead (row %d leaves); d[1:] around the oracle's winner: %s" % (
+                e_dev, r_dev, _window_text(d[1:], e, e_dev))
+        return msg + "the device's LEAVING row is %d instead (entering %d agrees); ratios around the oracle's winner: %s" % (
+            r_dev, e, _window_text(ratios(T, e), r, r_dev))
+
+    f1 = bad(1, bases1)
+    if p1 and f1(p1):
+        return report(1, _first_bad(0, p1, f1), T0, d0, base0, piv1, bases1) + " (device runs: %d)" % (len(runs) + 1)
+    if st1 != oracle.FEASIBLE or _negative(d1[0]) or np.any(base1 >= n + m):
+        return "the bases agree through phase 1 (%d pivots), which is where the oracle ends" % p1
+    T2, d2, base2 = phase2_state(T1.copy(), d1, base1.copy(), c)
+    piv2, bases2, _, _ = oracle_trace(T2, d2, base2, 1 << 40)
+    p2 = len(piv2)
+    f2 = bad(2, bases2)
+    if p2 <= p1:
+        return "the bases agree through phase 1 (%d pivots); phase 2 (%d pivots) is no longer than phase 1, so the " \
+            "pivot cap cannot stop inside it" % (p1, p2)
+    if not f2(p2):
+        return "the bases agree through phase 1 (%d pivots) and after %d pivots of phase 2: the same pivots as far " \
+            "as the basis tells, different arithmetic" % (p1, p2)
+    if f2(p1 + 1):
+        return "the bases agree through phase 1 (%d pivots) and differ after %d pivots of phase 2, the smallest count " \
+            "the pivot cap can stop phase 2 at" % (p1, p1 + 1)
+    return report(2, _first_bad(p1 + 1, p2, f2), T2, d2, base2, piv2, bases2) + " (device runs: %d)" % (len(runs) + 1)
