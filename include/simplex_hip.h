@@ -230,6 +230,44 @@ long long simplex_batch_device_workspace(int n, int m, int count);
  * dimension longer than 1, -5 workspace NULL, misaligned or too small */
 int simplex_solve_batch_device(const simplex_batch_device_t *args);
 
+/* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
+/* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through
+ * element strides (a transposed or sliced view is not copied), each shard builds its rows of the
+ * phase-1 tableau straight from them, and the results are left on the device.  No host copy and no
+ * second device copy of A is made (copies of O(m + n) are); one 4-byte read-back decides slack
+ * compaction by twoPhaseMethodEx's rule (no b[i] < 0.0).  Every shard setting is honoured as in
+ * twoPhaseMethodEx (virtual ranks, a SIMPLEX_GPUS / simplex_set_gpus list, RCCL ranks each holding
+ * the whole problem; blocked / row-major storage, regions, alias, compaction, deactivation).
+ * A, b and c must lie on the engine's primary device -- the current device (simplex_set_device), or
+ * the first of the device list -- whose peers read them through peer access; so must the outputs.
+ * Result: twoPhaseMethodEx's for the same values, bit for bit -- *status_out (engine-only statuses
+ * included), pivots_out[2], base[m]; *opt_out and x[n] as simplex_solve_batch_device writes them (the
+ * objective and getSolutionHost when FEASIBLE, else a quiet NaN and all +0.0, never stale memory);
+ * objrow is what simplex_last_objective_row reports: *row_width_out entries (1+n+m after phase 2,
+ * 1+n+2m when phase 1 ended the solve, a pivot cap included), +0.0 from there up to 1+n+2m.
+ * simplex_last_objective_row, simplex_last_phase_seconds, the TIMER CSV and the verbose lines are
+ * twoPhaseMethodEx's.  opt_out and row_width_out may be NULL.
+ * The call is synchronous: it waits for `stream` on the host before reading the inputs and returns
+ * after all engine work has finished, so the outputs may be used on any stream.  The inputs are
+ * not written; the outputs must not overlap them or each other (not checked). */
+typedef struct {
+    int n, m;                               /* n variables x m constraints, any shape with n >= 1, m >= 1 */
+    const double *A; long long A_sr, A_sc;  /* device; element strides: row (constraint), column (variable) */
+    const double *b; long long b_si;
+    const double *c; long long c_sj;
+    long long max_pivots;                   /* as twoPhaseMethodEx */
+    double *x;        /* device [n]       or NULL */
+    int *base;        /* device [m]       or NULL */
+    double *objrow;   /* device [1+n+2m]  or NULL */
+    void *stream;     /* hipStream_t the inputs were produced on; NULL = the null stream */
+} simplex_device_solve_t;
+
+/* returns 0, -1 args, status_out or pivots_out NULL, -3 n < 1 or m < 1, -2 A, b or c NULL, -4 a
+ * stride of 0 on a dimension longer than 1 (all decided before any device is touched), -6 A, b or
+ * c not in device memory of the engine's primary device (hipPointerGetAttributes) */
+int simplex_solve_device(const simplex_device_solve_t *args, int *status_out, double *opt_out,
+                         long long *pivots_out /*[2]*/, int *row_width_out);
+
 /* problem_t from caller arrays (copied; A column-major m x n); free with freeProblem()
  * and then free() of the struct, as the reference's callers do. */
 problem_t *simplex_problem_from_arrays(int n, int m, const double *A_colmajor, const double *b,
@@ -341,6 +379,10 @@ int simplex_dev_build_phase1(problem_t *problem, double *T, long long ld, double
 /* the same from the device generator */
 int simplex_dev_build_phase1_generated(int n, int m, unsigned int seed, int lo, int hi, double *T, long long ld,
                                        double *d, int *base);
+/* the same from device arrays, as simplex_solve_device builds it (A, b: device memory read through
+ * element strides; T, d, base: host); returns 0 or simplex_solve_device's -3, -2, -4, -6 */
+int simplex_dev_build_phase1_device(int n, int m, const double *A, long long A_sr, long long A_sc, const double *b,
+                                    long long b_si, double *T, long long ld, double *d, int *base);
 
 #ifdef __cplusplus
 }

@@ -13,5 +13,6 @@ from .api import (  # noqa: F401
     set_blocked, set_fine_pivot_rows, set_gpus, set_p2p, set_regions, set_replicated_objective, set_sweep_mfma,
     set_update_waves, set_verbose, set_virtual_ranks,
     BatchTensors, batch_class, batch_counts, set_batch_budget, solve_batch, solve_batch_tensors,
+    SolveTensors, dev_build_phase1_tensors, solve_tensors,
     twoPhaseMethod, twoPhaseMethodEx)
 from ._lib import LIB_PATH, load  # noqa: F401

@@ -74,6 +74,19 @@ class BatchDeviceT(ctypes.Structure):
     ]
 
 
+class DeviceSolveT(ctypes.Structure):
+    """simplex_device_solve_t (include/simplex_hip.h); every pointer is a device address."""
+    _fields_ = [
+        ("n", ctypes.c_int), ("m", ctypes.c_int),
+        ("A", ctypes.c_void_p), ("A_sr", ctypes.c_longlong), ("A_sc", ctypes.c_longlong),
+        ("b", ctypes.c_void_p), ("b_si", ctypes.c_longlong),
+        ("c", ctypes.c_void_p), ("c_sj", ctypes.c_longlong),
+        ("max_pivots", ctypes.c_longlong),
+        ("x", ctypes.c_void_p), ("base", ctypes.c_void_p), ("objrow", ctypes.c_void_p),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
 P_PROBLEM = ctypes.POINTER(ProblemT)
 P_TABULAR = ctypes.POINTER(TabularT)
 
@@ -142,6 +155,7 @@ SIGNATURES = {
     "simplex_set_batch_budget": (None, [ctypes.c_longlong]),
     "simplex_batch_device_workspace": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "simplex_solve_batch_device": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT)]),
+    "simplex_solve_device": (ctypes.c_int, [ctypes.POINTER(DeviceSolveT), c_int_p, c_double_p, c_ll_p, c_int_p]),
     "simplex_problem_from_arrays": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "simplex_generate_problem_ex": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int]),
@@ -184,6 +198,9 @@ SIGNATURES = {
     "simplex_dev_update_objective": (ctypes.c_int, [c_double_p, ctypes.c_longlong, ctypes.c_longlong,
                                                     ctypes.c_longlong, c_int_p, c_double_p]),
     "simplex_dev_build_phase1": (ctypes.c_int, [P_PROBLEM, c_double_p, ctypes.c_longlong, c_double_p, c_int_p]),
+    "simplex_dev_build_phase1_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
+                                                       ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
+                                                       c_double_p, ctypes.c_longlong, c_double_p, c_int_p]),
 }
 
 _lib = None

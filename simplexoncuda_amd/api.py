@@ -332,6 +332,102 @@ def _finish_evicted(out, A, b, c, max_pivots):
             out.row_width[k] = len(d)
 
 
+@dataclass
+class SolveTensors:
+    """solve_tensors' result.  status, pivots and optimal_value are host values; solution, base and
+    objective_row are tensors on the inputs' device.  Unless the status is FEASIBLE optimal_value is
+    NaN and solution is zero; objective_row (when asked for) holds row_width entries of the final
+    objective row, zero-padded to 1 + n + 2m."""
+    status: int
+    pivots: tuple          # (phase 1, phase 2)
+    optimal_value: float
+    solution: object       # float64 [n]
+    base: object           # int32 [m]
+    objective_row: object  # float64 [1 + n + 2m], or None
+    row_width: int         # 1 + n + m after phase 2, 1 + n + 2m when phase 1 ended the solve
+
+    @property
+    def status_name(self):
+        return STATUS_NAMES.get(self.status, str(self.status))
+
+    @property
+    def reduced_costs(self):
+        """objective_row[1 : 1+n] (a view): (A^T y - c)_j after a FEASIBLE solve."""
+        n = self.solution.shape[0]
+        return self.objective_row[1:1 + n]
+
+    @property
+    def duals(self):
+        """objective_row[1+n : 1+n+m] (a view): the dual y_i of constraint i after a FEASIBLE solve."""
+        n, m = self.solution.shape[0], self.base.shape[0]
+        return self.objective_row[1 + n:1 + n + m]
+
+
+def _check_device_problem(fn, A, b, c):
+    """solve_tensors' input checks (c None: the build hook's); returns (m, n)"""
+    import torch
+
+    for name, t in (("A", A), ("b", b), ("c", c)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{fn}: {name} must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype != torch.float64:
+            raise TypeError(f"{fn}: {name} must be float64, not {t.dtype}")
+    if A.dim() != 2 or b.dim() != 1 or (c is not None and c.dim() != 1):
+        raise ValueError(f"{fn}: A must be [m, n], b [m] and c [n]")
+    m, n = A.shape
+    if tuple(b.shape) != (m,) or (c is not None and tuple(c.shape) != (n,)):
+        raise ValueError(f"{fn}: A is {tuple(A.shape)}, so b must be {(m,)} and c {(n,)}; "
+                         f"got {tuple(b.shape)} and {None if c is None else tuple(c.shape)}")
+    if n < 1 or m < 1 or n >= 2 ** 31 or m >= 2 ** 31:
+        raise ValueError(f"{fn}: a problem needs at least one variable and one constraint, not {n} x {m}")
+    if A.device.type != "cuda":
+        raise ValueError(f"{fn}: A is on {A.device}; the tensors must be on a GPU")
+    if b.device != A.device or (c is not None and c.device != A.device):
+        raise ValueError(f"{fn}: A, b and c must be on the same device")
+    return m, n
+
+
+def solve_tensors(A, b, c, max_pivots=-1, objective_row=False):
+    """twoPhaseMethodEx of one problem held in device tensors (simplex_solve_device): A [m, n], b [m],
+    c [n], float64 on one ROCm device -- the engine's primary device -- read in place through their
+    strides (a transposed or sliced view is not copied; no host copy and no second device copy of A
+    is made).  Any shape; every shard setting is honoured as in twoPhaseMethodEx.  The call is
+    synchronous: it waits for torch's current stream of that device before reading the inputs, and
+    the outputs may be used on any stream when it returns.  Returns a SolveTensors."""
+    import torch
+
+    m, n = _check_device_problem("solve_tensors", A, b, c)
+    lib = _lib.load()
+    dev = A.device
+    N1 = 1 + n + 2 * m
+    with torch.cuda.device(dev):
+        x = torch.empty(n, dtype=torch.float64, device=dev)
+        base = torch.empty(m, dtype=torch.int32, device=dev)
+        row = torch.empty(N1, dtype=torch.float64, device=dev) if objective_row else None
+        args = _lib.DeviceSolveT(
+            n=n, m=m,
+            A=A.data_ptr(), A_sr=A.stride(0), A_sc=A.stride(1),
+            b=b.data_ptr(), b_si=b.stride(0),
+            c=c.data_ptr(), c_sj=c.stride(0),
+            max_pivots=max_pivots,
+            x=x.data_ptr(), base=base.data_ptr(), objrow=row.data_ptr() if objective_row else None,
+            stream=torch.cuda.current_stream(dev).cuda_stream)
+        status = ctypes.c_int(0)
+        opt = ctypes.c_double(0.0)
+        piv = (ctypes.c_longlong * 2)()
+        width = ctypes.c_int(0)
+        rc = lib.simplex_solve_device(ctypes.byref(args), ctypes.byref(status), ctypes.byref(opt), piv,
+                                      ctypes.byref(width))
+    if rc == -6:
+        raise ValueError(f"solve_tensors: the tensors are on {dev}, not on the engine's primary device "
+                         "(the current device, or the first of the SIMPLEX_GPUS / set_gpus list)")
+    if rc < 0:
+        raise ValueError(f"simplex_solve_device: bad arguments ({rc})")
+    return SolveTensors(status.value, (piv[0], piv[1]), opt.value, x, base, row, width.value)
+
+
 def batch_class(n, m):
     """Where solve_batch runs a problem of n variables and m constraints: 2 LDS-resident,
     1 workspace-resident, 0 the engine (host arithmetic only)."""
@@ -510,6 +606,26 @@ def dev_build_phase1(problem):
     base = np.zeros(max(m, 1), dtype=np.int32)
     lib.simplex_dev_build_phase1(problem.ptr, _dp(T), N1, _dp(d), _ip(base))
     return T, d, base[:m]
+
+
+def dev_build_phase1_tensors(A, b):
+    """The phase-1 tableau as solve_tensors builds it from device tensors A [m, n], b [m] (read in
+    place through their strides), in logical columns on the host: (T, d, base), as dev_build_phase1."""
+    import torch
+
+    m, n = _check_device_problem("dev_build_phase1_tensors", A, b, None)
+    lib = _lib.load()
+    N1 = 1 + n + 2 * m
+    T = np.zeros((m, N1))
+    d = np.zeros(N1)
+    base = np.zeros(m, dtype=np.int32)
+    with torch.cuda.device(A.device):
+        torch.cuda.current_stream(A.device).synchronize()  # (the hook takes no stream)
+        rc = lib.simplex_dev_build_phase1_device(n, m, A.data_ptr(), A.stride(0), A.stride(1), b.data_ptr(),
+                                                 b.stride(0), _dp(T), N1, _dp(d), _ip(base))
+    if rc < 0:
+        raise ValueError(f"simplex_dev_build_phase1_device: bad arguments ({rc})")
+    return T, d, base
 
 
 def dev_build_phase1_generated(n, m, seed, lo, hi):

@@ -289,6 +289,17 @@ void sx_launch_gemv_apply(double *d, Cols c, const double *partials, int nblk, h
 
 void sx_launch_build_rows(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const double *A_local,
                           const double *b_full, hipStream_t s);
+// the same tableau (stored columns [0, Ns) of the shard's rows) in one pass from a caller's device
+// arrays: A(i, j) = A[i * A_sr + j * A_sc], b_i = b[i * b_si] (element strides, 64-bit)
+void sx_launch_build_strided(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const double *A,
+                             long long A_sr, long long A_sc, const double *b, long long b_si, hipStream_t s);
+void sx_launch_copy_strided(double *dst, const double *src, long long stride, int count, hipStream_t s);
+// *flag (zero at launch) = 1 when some b_i < 0.0
+void sx_launch_any_negative(const double *b, long long b_si, int m, int *flag, hipStream_t s);
+// dst[0, w) = src[0, w), dst[w, total) = +0.0
+void sx_launch_copy_pad(double *dst, const double *src, int w, int total, hipStream_t s);
+// x[base[i]] = rhs[i] for base[i] < n (x zero at launch)
+void sx_launch_scatter_solution(double *x, int n, const int *base, const double *rhs, int m, hipStream_t s);
 void sx_launch_init_vectors(double *d, int N1, int n, int m, int *base, hipStream_t s);
 void sx_launch_phase2_costs(double *d, int n, int m, const double *c, hipStream_t s);
 void sx_launch_gather_rhs(const double *T, int rows, TLay tl, double *out, hipStream_t s);

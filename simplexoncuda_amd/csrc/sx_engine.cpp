@@ -15,6 +15,7 @@
 #include <cstring>
 #include <ctime>
 #include <functional>
+#include <limits>
 #include <map>
 #include <string>
 #include <mutex>
@@ -921,6 +922,31 @@ class Engine {
         set_compact(nonneg);
     }
 
+    // the same tableau as build_phase1 of the same values, from a caller's device arrays on the
+    // primary device (simplex_solve_device; c null: the parity hook, no costs): every shard builds
+    // its rows straight from them in one pass -- no host copy and no second device copy of A -- and
+    // one int read back decides compaction by build_phase1's rule
+    void build_phase1_device(const double *A, long long A_sr, long long A_sc, const double *b, long long b_si,
+                             const double *c, long long c_sj) {
+        int *neg = dalloc<int>(1);
+        SX_HIP(hipMemsetAsync(neg, 0, sizeof(int), s));
+        sx_launch_any_negative(b, b_si, m, neg, s);
+        if (c != nullptr) {
+            if (!c_dev) c_dev = dalloc<double>(n);
+            sx_launch_copy_strided(c_dev, c, c_sj, n, s);
+        }
+        for (auto &x : sh) {
+            DevGuard g(x.dev);
+            sx_launch_build_strided(x.T, x.rows, x.row0, tl, n, m, Ns1, A, A_sr, A_sc, b, b_si, x.s);
+            sx_launch_init_vectors(x.d, N1, n, m, x.base, x.s);
+        }
+        int any_neg = 0;
+        SX_HIP(hipMemcpyAsync(&any_neg, neg, sizeof(int), hipMemcpyDeviceToHost, s));
+        sync_all();
+        (void)hipFree(neg);
+        set_compact(any_neg == 0);
+    }
+
     // the same tableau as build_phase1(generateRandomProblem(n, m, seed, lo, hi)), synthesised
     // on the device: every shard generates only its own rows (jump-ahead XORWOW)
     void build_phase1_generated(unsigned seed, int lo, int hi, int rand_kind) {
@@ -1706,17 +1732,33 @@ class Engine {
     // RHS column of all rows (for the solution, getSolution twoPhaseMethod.cu:116-128)
     void read_rhs(std::vector<double> &out) {
         out.assign(m, 0.0);
+        SX_HIP(hipMemcpyAsync(out.data(), gather_rhs(), sizeof(double) * m, hipMemcpyDeviceToHost, s));
+        SX_HIP(hipStreamSynchronize(s));
+    }
+
+    // ... gathered on the first shard's device (enqueued on the engine stream s)
+    const double *gather_rhs() {
         for (auto &x : sh) {
             DevGuard g(x.dev);
             sx_launch_gather_rhs(x.T, x.rows, tl, x.rhs_local, x.s);
         }
-        if (xchg) {
-            allgather_doubles(&Shard::rhs_local, &Shard::rhs_all, rpr);
-            SX_HIP(hipMemcpyAsync(out.data(), sh[0].rhs_all, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-        } else {
-            SX_HIP(hipMemcpyAsync(out.data(), sh[0].rhs_local, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+        if (!xchg) return sh[0].rhs_local;
+        allgather_doubles(&Shard::rhs_local, &Shard::rhs_all, rpr);
+        return sh[0].rhs_all;
+    }
+
+    // simplex_solve_device's results, left in the caller's device memory (the primary device's, any
+    // of them null): the basis, the objective row d[0, width) zero-padded to N1 (width: what read_d
+    // took, so the row is whole on the first shard), and x -- getSolutionHost when `feasible`, else
+    // all +0.0.  Enqueued on the engine stream; the caller synchronises.
+    void write_results(double *x_out, int *base_dev, double *objrow, int width, bool feasible) {
+        Shard &x0 = sh[0];
+        if (base_dev) SX_HIP(hipMemcpyAsync(base_dev, x0.base, sizeof(int) * m, hipMemcpyDeviceToDevice, s));
+        if (objrow) sx_launch_copy_pad(objrow, x0.d, width, N1, s);
+        if (x_out) {
+            sx_launch_copy_pad(x_out, nullptr, 0, n, s);
+            if (feasible) sx_launch_scatter_solution(x_out, n, x0.base, gather_rhs(), m, s);
         }
-        SX_HIP(hipStreamSynchronize(s));
     }
 
     // rows of the whole tableau (virtual or single shard only), logical columns: for tests
@@ -1875,9 +1917,12 @@ static double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-int two_phase(problem_t *P, double *solution, double *opt, int *base_out, long long *pivots_out,
-              long long max_pivots) {
-    const int n = P->vars, m = P->constraints;
+// The problem comes from a host problem_t (P; the results go to the host arrays) or from a caller's
+// device arrays (D, simplex_solve_device; the results stay on the device): only the build and the
+// epilogue differ.
+int two_phase(problem_t *P, const simplex_device_solve_t *D, double *solution, double *opt, int *base_out,
+              long long *pivots_out, long long max_pivots, int *row_width_out) {
+    const int n = P ? P->vars : D->n, m = P ? P->constraints : D->m;
     Engine E(n, m);
     Chrono ch;
     ch.open(n, m);
@@ -1886,7 +1931,10 @@ int two_phase(problem_t *P, double *solution, double *opt, int *base_out, long l
     // phase1 (twoPhaseMethod.cu:225-283)
     say("Phase 1: Filling Tableau");
     ch.start(E.s, E.N1, m, "fillTableau");
-    E.build_phase1(P);
+    if (P)
+        E.build_phase1(P);
+    else
+        E.build_phase1_device(D->A, D->A_sr, D->A_sc, D->b, D->b_si, D->c, D->c_sj);
     ch.stop(E.s);
     say("Phase 1: Resetting out-of-base variables");
     if (debug_on()) {
@@ -1952,16 +2000,31 @@ int two_phase(problem_t *P, double *solution, double *opt, int *base_out, long l
             // getSolutionHost (:370-383)
             ch.start(E.s, E.N2, m, "solution");
             const double z = E.read_d0();
-            std::vector<double> rhs;
-            E.read_rhs(rhs);
-            if (opt) *opt = z;
-            if (solution) {
-                for (int j = 0; j < n; ++j) solution[j] = 0.0;
-                for (int i = 0; i < m; ++i)
-                    if (base[i] < n) solution[base[i]] = rhs[i];
+            if (P) {
+                std::vector<double> rhs;
+                E.read_rhs(rhs);
+                if (opt) *opt = z;
+                if (solution) {
+                    for (int j = 0; j < n; ++j) solution[j] = 0.0;
+                    for (int i = 0; i < m; ++i)
+                        if (base[i] < n) solution[base[i]] = rhs[i];
+                }
+            } else {
+                if (opt) *opt = z;
+                E.write_results(D->x, D->base, D->objrow, E.N2, true);
+                E.sync_all();
             }
             ch.stop(E.s);
         }
+    }
+    if (D) {
+        // (every other outcome: the basis and the row as they are, a quiet NaN and x all +0.0)
+        if (status != FEASIBLE) {
+            if (opt) *opt = std::numeric_limits<double>::quiet_NaN();
+            E.write_results(D->x, D->base, D->objrow, (int)g_last_d.size(), false);
+            E.sync_all();
+        }
+        if (row_width_out) *row_width_out = (int)g_last_d.size();
     }
     if (base_out) std::memcpy(base_out, base.data(), sizeof(int) * m);
     if (pivots_out) {
@@ -1969,6 +2032,11 @@ int two_phase(problem_t *P, double *solution, double *opt, int *base_out, long l
         pivots_out[1] = p2;
     }
     return status;
+}
+
+int two_phase(problem_t *P, double *solution, double *opt, int *base_out, long long *pivots_out,
+              long long max_pivots) {
+    return two_phase(P, nullptr, solution, opt, base_out, pivots_out, max_pivots, nullptr);
 }
 
 // A small instance solved with the multi-rank fused batch over peer memory -- in one-stage (32) and
@@ -2201,6 +2269,56 @@ int twoPhaseMethod(problem_t *problem, TYPE *solution, TYPE *optimalValue) {
 int twoPhaseMethodEx(problem_t *problem, double *solution, double *optimalValue, int *base_out,
                      long long *pivots_out, long long max_pivots) {
     return two_phase(problem, solution, optimalValue, base_out, pivots_out, max_pivots);
+}
+
+// ---------------------------------------------------------------- one large LP from device arrays
+// the host-only argument checks of simplex_solve_device and its parity hook
+static int device_source_check(int n, int m, const double *A, long long A_sr, long long A_sc, const double *b,
+                               long long b_si, const double *c, long long c_sj, bool need_c) {
+    if (n < 1 || m < 1) return -3;
+    if (A == nullptr || b == nullptr || (need_c && c == nullptr)) return -2;
+    // a stride of 0 would alias the elements of a dimension that has more than one
+    if ((m > 1 && (A_sr == 0 || b_si == 0)) || (n > 1 && (A_sc == 0 || (need_c && c_sj == 0)))) return -4;
+    return 0;
+}
+
+// the device a new Engine's first shard will live on (the Engine constructor's rule)
+static int primary_device() {
+    if (!g_cfg.single_shard && g_cfg.ipc_world <= 1 && !(g_cfg.dist && g_cfg.comm)) {
+        const std::vector<int> devs = shard_devices();
+        if (devs.size() > 1) return devs[0];
+    }
+    if (g_cfg.device >= 0) return g_cfg.device;
+    int dev = 0;
+    SX_HIP(hipGetDevice(&dev));
+    return dev;
+}
+
+static bool on_device(const void *p, int dev) {
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // (a plain host pointer)
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice && at.device == dev;
+}
+
+int simplex_solve_device(const simplex_device_solve_t *args, int *status_out, double *opt_out,
+                         long long *pivots_out, int *row_width_out) {
+    if (args == nullptr || status_out == nullptr || pivots_out == nullptr) return -1;
+    const int rc = device_source_check(args->n, args->m, args->A, args->A_sr, args->A_sc, args->b, args->b_si,
+                                       args->c, args->c_sj, true);
+    if (rc != 0) return rc;
+    const int dev = primary_device();
+    if (!on_device(args->A, dev) || !on_device(args->b, dev) || !on_device(args->c, dev)) return -6;
+    {
+        // the inputs are complete before any engine stream reads them
+        DevGuard g(dev);
+        SX_HIP(hipStreamSynchronize(static_cast<hipStream_t>(args->stream)));
+    }
+    *status_out = two_phase(nullptr, args, nullptr, opt_out, nullptr, pivots_out, args->max_pivots, row_width_out);
+    return 0;
 }
 
 // ---------------------------------------------------------------- batched solve
@@ -2984,6 +3102,23 @@ int simplex_dev_build_phase1_generated(int n, int m, unsigned int seed, int lo, 
 int simplex_dev_build_phase1(problem_t *problem, double *T, long long ld, double *d, int *base) {
     Engine E(problem->vars, problem->constraints);
     E.build_phase1(problem);
+    E.download(T, (size_t)ld, E.N1, d);
+    E.read_base(base);
+    return 0;
+}
+
+int simplex_dev_build_phase1_device(int n, int m, const double *A, long long A_sr, long long A_sc, const double *b,
+                                    long long b_si, double *T, long long ld, double *d, int *base) {
+    const int rc = device_source_check(n, m, A, A_sr, A_sc, b, b_si, nullptr, 0, false);
+    if (rc != 0) return rc;
+    const int dev = primary_device();
+    if (!on_device(A, dev) || !on_device(b, dev)) return -6;
+    {
+        DevGuard g(dev);
+        SX_HIP(hipStreamSynchronize(nullptr));
+    }
+    Engine E(n, m);
+    E.build_phase1_device(A, A_sr, A_sc, b, b_si, nullptr, 0);
     E.download(T, (size_t)ld, E.N1, d);
     E.read_base(base);
     return 0;

@@ -3292,6 +3292,104 @@ __global__ void k_init_vectors(double *d, int N1, int n, int m, int *base) {
     if (t < m) base[t] = n + m + t;
 }
 
+// The whole phase-1 tableau of a shard -- k_fill_structural and k_fill_rows in one pass -- straight
+// from a caller's device arrays read through element strides (simplex_solve_device): stored
+// column 0 = b, 1 + j = A(:, j), then the slack (and, without aliasing, artificial) identities,
+// the row negated where compare(b_i) < 0 exactly as k_fill_rows does (its zeros become -0.0).
+// One block builds a 16-row strip x SX_BUILD_COLS stored columns.  Tiles that hold structural
+// columns are staged through a padded LDS tile so that both sides move whole lines: consecutive
+// lanes walk the source along its smaller stride (walk_i, uniform over the launch: along i for a
+// transposed view, else along j), and the write is consecutive 16-byte stores -- in the blocked
+// layout a strip's column range is one contiguous run of 4x4 blocks, so lane k stores the pair at
+// offset 2k of that run (TLay::idx only names the address; jB and SX_BUILD_COLS keep a tile inside
+// one region).  Tiles behind the structural columns store their identity values directly.
+#define SX_BUILD_COLS 256
+__global__ __launch_bounds__(256) void k_build_strided(double *__restrict__ T, int rows, int row0, TLay tl, int n, int m,
+                                                       int Ns, const double *__restrict__ A, long long A_sr,
+                                                       long long A_sc, const double *__restrict__ b, long long b_si,
+                                                       int walk_i) {
+    __shared__ double tile[16][SX_BUILD_COLS + 1];
+    __shared__ double sb[16];
+    const int t = threadIdx.x;
+    const int i0 = blockIdx.y * 16, j0 = blockIdx.x * SX_BUILD_COLS;
+    const int nr = min(16, rows - i0);
+    if (t < 16) sb[t] = t < nr ? b[(long long)(row0 + i0 + t) * b_si] : 0.0;
+    __syncthreads();
+    // stored column j < Ns of the strip's row r < nr
+    auto value = [&](int r, int j) -> double {
+        const int gi = row0 + i0 + r;
+        const double bi = sb[r];
+        double x;
+        if (j == 0)
+            x = bi;
+        else if (j <= n)
+            x = A[(long long)gi * A_sr + (long long)(j - 1) * A_sc];
+        else
+            x = (j == 1 + n + gi || j == 1 + n + m + gi) ? 1.0 : 0.0;
+        return cmp_eps(bi, 0.0) < 0 ? -x : x;
+    };
+    const bool staged = j0 <= n;  // (uniform over the block)
+    if (staged) {
+        if (walk_i) {
+            const int r = t & 15;
+            for (int cc = t >> 4; cc < SX_BUILD_COLS; cc += 16)
+                if (r < nr && j0 + cc < Ns) tile[r][cc] = value(r, j0 + cc);
+        } else {
+            for (int r = 0; r < nr; ++r)
+                if (j0 + t < Ns) tile[r][t] = value(r, j0 + t);
+        }
+        __syncthreads();
+    }
+    for (int k = t; k < 16 * SX_BUILD_COLS / 2; k += 256) {
+        int r, cc;
+        if (tl.blk) {  // offset 2k of the strip's run of blocks: group, row block, row, column pair
+            r = ((k >> 3) & 3) * 4 + ((k >> 1) & 3);
+            cc = (k >> 5) * 4 + (k & 1) * 2;
+        } else {
+            r = k / (SX_BUILD_COLS / 2);
+            cc = (k % (SX_BUILD_COLS / 2)) * 2;
+        }
+        const int j = j0 + cc;
+        if (r >= nr || j >= Ns) continue;
+        double *dst = &T[tl.idx(i0 + r, j)];
+        const double v0 = staged ? tile[r][cc] : value(r, j);
+        if (j + 1 < Ns) {
+            const double v1 = staged ? tile[r][cc + 1] : value(r, j + 1);
+            *reinterpret_cast<double2 *>(dst) = make_double2(v0, v1);
+        } else {
+            *dst = v0;
+        }
+    }
+}
+
+// dst[k] = src[k * stride], k < count (the objective coefficients of simplex_solve_device)
+__global__ void k_copy_strided(double *__restrict__ dst, const double *__restrict__ src, long long stride, int count) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < count) dst[k] = src[(long long)k * stride];
+}
+
+// *flag = 1 when some b_i < 0.0 (build_phase1's rule for slack compaction); *flag is zero at launch
+__global__ void k_any_negative(const double *__restrict__ b, long long b_si, int m, int *flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m && b[(long long)i * b_si] < 0.0) *flag = 1;
+}
+
+// dst[0, w) = src[0, w), dst[w, total) = +0.0 (w = 0: all zero; src is then not read)
+__global__ void k_copy_pad(double *__restrict__ dst, const double *__restrict__ src, int w, int total) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < total) dst[j] = j < w ? src[j] : 0.0;
+}
+
+// getSolutionHost (twoPhaseMethod.cu:370-383) on the device: x (zero at launch) takes the RHS of
+// every row whose basic variable is structural
+__global__ void k_scatter_solution(double *__restrict__ x, int n, const int *__restrict__ base,
+                                   const double *__restrict__ rhs, int m) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int v = base[i];
+    if (v >= 0 && v < n) x[v] = rhs[i];
+}
+
 // Phase-2 costs (twoPhaseMethod.cu:306-318): d[1..n] = -c, d[n+1..n+m] = 0, d[0] kept.
 __global__ void k_phase2_costs(double *d, int n, int m, const double *c) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3707,6 +3805,35 @@ void sx_launch_build_rows(double *T, int rows, int row0, TLay tl, int n, int m, 
     if (gx > 64) gx = 64;
     dim3 rg(gx, rows);
     k_fill_rows<<<rg, 256, 0, s>>>(T, rows, row0, tl, n, m, Ns, b_full);
+}
+
+void sx_launch_build_strided(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const double *A,
+                             long long A_sr, long long A_sc, const double *b, long long b_si, hipStream_t s) {
+    if (rows <= 0) return;
+    if (tl.jB < Ns && tl.jB % SX_BUILD_COLS != 0) SX_FATAL("region boundary inside a build tile");
+    const int walk_i = std::llabs(A_sc) > std::llabs(A_sr) ? 1 : 0;
+    dim3 grid((Ns + SX_BUILD_COLS - 1) / SX_BUILD_COLS, (rows + 15) / 16);
+    k_build_strided<<<grid, 256, 0, s>>>(T, rows, row0, tl, n, m, Ns, A, A_sr, A_sc, b, b_si, walk_i);
+}
+
+void sx_launch_copy_strided(double *dst, const double *src, long long stride, int count, hipStream_t s) {
+    if (count <= 0) return;
+    k_copy_strided<<<(count + 255) / 256, 256, 0, s>>>(dst, src, stride, count);
+}
+
+void sx_launch_any_negative(const double *b, long long b_si, int m, int *flag, hipStream_t s) {
+    if (m <= 0) return;
+    k_any_negative<<<(m + 255) / 256, 256, 0, s>>>(b, b_si, m, flag);
+}
+
+void sx_launch_copy_pad(double *dst, const double *src, int w, int total, hipStream_t s) {
+    if (total <= 0) return;
+    k_copy_pad<<<(total + 255) / 256, 256, 0, s>>>(dst, src, w, total);
+}
+
+void sx_launch_scatter_solution(double *x, int n, const int *base, const double *rhs, int m, hipStream_t s) {
+    if (m <= 0) return;
+    k_scatter_solution<<<(m + 255) / 256, 256, 0, s>>>(x, n, base, rhs, m);
 }
 
 void sx_launch_init_vectors(double *d, int N1, int n, int m, int *base, hipStream_t s) {
