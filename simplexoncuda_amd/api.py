@@ -246,26 +246,13 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     refused: solve_batch takes those."""
     import torch
 
-    for name, t in (("A", A), ("b", b), ("c", c)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"solve_batch_tensors: {name} must be a torch.Tensor, not {type(t).__name__}")
-        if t.dtype != torch.float64:
-            raise TypeError(f"solve_batch_tensors: {name} must be float64, not {t.dtype}")
-    if A.dim() != 3 or b.dim() != 2 or c.dim() != 2:
-        raise ValueError("solve_batch_tensors: A must be [B, m, n], b [B, m] and c [B, n]")
-    B, m, n = A.shape
-    if tuple(b.shape) != (B, m) or tuple(c.shape) != (B, n):
-        raise ValueError(f"solve_batch_tensors: A is {tuple(A.shape)}, so b must be {(B, m)} and c {(B, n)}; "
-                         f"got {tuple(b.shape)} and {tuple(c.shape)}")
+    B, m, n = _check_device_shapes("solve_batch_tensors", A, b, c, batch=True)
     if B >= 2 ** 31:
         raise ValueError("solve_batch_tensors: too many problems for one call")
     if n < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
         raise ValueError(f"solve_batch_tensors: a problem of {n} variables x {m} constraints is not solved by a "
                          "resident workgroup; use solve_batch for such shapes")
-    if A.device.type != "cuda":
-        raise ValueError(f"solve_batch_tensors: A is on {A.device}; the tensors must be on a GPU")
-    if b.device != A.device or c.device != A.device:
-        raise ValueError("solve_batch_tensors: A, b and c must be on the same device")
+    _check_device_placement("solve_batch_tensors", A, b, c)
     lib = _lib.load()
     dev = A.device
     N1 = 1 + n + 2 * m
@@ -363,30 +350,37 @@ class SolveTensors:
         return self.objective_row[1 + n:1 + n + m]
 
 
-def _check_device_problem(fn, A, b, c):
-    """solve_tensors' input checks (c None: the build hook's); returns (m, n)"""
+def _check_device_shapes(fn, A, b, c, batch=False):
+    """Types and shapes of a problem in device tensors, with one more leading dimension B when batch;
+    returns A's shape.  c may be None for one problem (the build hook's case).  The rule on n and m
+    themselves is the caller's when batch."""
     import torch
 
     for name, t in (("A", A), ("b", b), ("c", c)):
-        if t is None:
+        if t is None and name == "c" and not batch:
             continue
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{fn}: {name} must be a torch.Tensor, not {type(t).__name__}")
         if t.dtype != torch.float64:
             raise TypeError(f"{fn}: {name} must be float64, not {t.dtype}")
-    if A.dim() != 2 or b.dim() != 1 or (c is not None and c.dim() != 1):
-        raise ValueError(f"{fn}: A must be [m, n], b [m] and c [n]")
-    m, n = A.shape
-    if tuple(b.shape) != (m,) or (c is not None and tuple(c.shape) != (n,)):
-        raise ValueError(f"{fn}: A is {tuple(A.shape)}, so b must be {(m,)} and c {(n,)}; "
+    k, B = (1, "B, ") if batch else (0, "")
+    if A.dim() != k + 2 or b.dim() != k + 1 or (c is not None and c.dim() != k + 1):
+        raise ValueError(f"{fn}: A must be [{B}m, n], b [{B}m] and c [{B}n]")
+    lead, (m, n) = tuple(A.shape[:k]), A.shape[k:]
+    if tuple(b.shape) != lead + (m,) or (c is not None and tuple(c.shape) != lead + (n,)):
+        raise ValueError(f"{fn}: A is {tuple(A.shape)}, so b must be {lead + (m,)} and c {lead + (n,)}; "
                          f"got {tuple(b.shape)} and {None if c is None else tuple(c.shape)}")
-    if n < 1 or m < 1 or n >= 2 ** 31 or m >= 2 ** 31:
+    if not batch and (n < 1 or m < 1 or n >= 2 ** 31 or m >= 2 ** 31):
         raise ValueError(f"{fn}: a problem needs at least one variable and one constraint, not {n} x {m}")
+    return tuple(A.shape)
+
+
+def _check_device_placement(fn, A, b, c):
+    """A on a GPU, b and c (unless None) on the same one"""
     if A.device.type != "cuda":
         raise ValueError(f"{fn}: A is on {A.device}; the tensors must be on a GPU")
     if b.device != A.device or (c is not None and c.device != A.device):
         raise ValueError(f"{fn}: A, b and c must be on the same device")
-    return m, n
 
 
 def solve_tensors(A, b, c, max_pivots=-1, objective_row=False):
@@ -398,7 +392,8 @@ def solve_tensors(A, b, c, max_pivots=-1, objective_row=False):
     the outputs may be used on any stream when it returns.  Returns a SolveTensors."""
     import torch
 
-    m, n = _check_device_problem("solve_tensors", A, b, c)
+    m, n = _check_device_shapes("solve_tensors", A, b, c)
+    _check_device_placement("solve_tensors", A, b, c)
     lib = _lib.load()
     dev = A.device
     N1 = 1 + n + 2 * m
@@ -613,7 +608,8 @@ def dev_build_phase1_tensors(A, b):
     place through their strides), in logical columns on the host: (T, d, base), as dev_build_phase1."""
     import torch
 
-    m, n = _check_device_problem("dev_build_phase1_tensors", A, b, None)
+    m, n = _check_device_shapes("dev_build_phase1_tensors", A, b, None)
+    _check_device_placement("dev_build_phase1_tensors", A, b, None)
     lib = _lib.load()
     N1 = 1 + n + 2 * m
     T = np.zeros((m, N1))

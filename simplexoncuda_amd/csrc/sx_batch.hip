@@ -14,9 +14,11 @@
 // to its slack column (sx_common.hpp Cols), so T stores 1 + n + m columns and logical column
 // j >= 1 + n + m reads stored column j - m; d keeps the full width.
 //
-// Two entries share the device functions: k_batch_solve (simplex_solve_batch: ragged problems packed
-// by the host, results finished on the host) and k_batch_solve_dev (simplex_solve_batch_device: one
-// shape, strided device arrays in, every result written by the kernel).
+// The two-phase method is written once (WG_TWO_PHASE and its parts), over a strided source (sx_common.hpp
+// SxSource).  Its two entries differ only in where a problem comes from and where its results go:
+// k_batch_solve (simplex_solve_batch: ragged problems packed by the host -- column-major A, the
+// source with A_sr = 1, A_sc = m -- results finished on the host) and k_batch_solve_dev
+// (simplex_solve_batch_device: one shape, the caller's strides, every result written by the kernel).
 
 #include <float.h>
 
@@ -173,119 +175,8 @@ __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max
     }
 }
 
-template <bool LDS>
-__global__ __launch_bounds__(SX_TILE) void k_batch_solve(BatchArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    __shared__ double s_v[16];
-    __shared__ int s_i[16];
-    __shared__ double s_rv;
-    __shared__ int s_ri;
-    __shared__ unsigned s_k;
-    double *W;
-    if constexpr (LDS)
-        W = s_dyn;
-    else
-        W = a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    for (;;) {
-        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
-        __syncthreads();
-        const unsigned k = s_k;
-        if (k >= (unsigned)a.count) return;
-        const int id = a.order[k];
-        const BatchProb pb = a.probs[id];
-        const int n = pb.n, m = pb.m;
-        const BatchLay lay = sx_batch_lay(n, m);
-        BatchWork w;
-        w.T = W;
-        w.d = W + lay.d;
-        w.prow = W + lay.prow;
-        w.colE = W + lay.colE;
-        w.parts = reinterpret_cast<TilePart *>(W + lay.parts);
-        w.base = reinterpret_cast<int *>(W + lay.base);
-        w.n = n;
-        w.m = m;
-        w.ld = lay.ld;
-        const int ld = lay.ld, Ns = 1 + n + m, N1 = Ns + m;
-        const double *A = a.in + pb.in_off, *bv = A + (size_t)n * m, *cv = bv + m;
-        const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
-
-        // orc_build_phase1: RHS, A, slack (the artificial block aliases it); a row with
-        // compare(b_i) < 0 is negated across all its entries, zeros included
-        for (int x = threadIdx.x; x < n * m; x += SX_TILE) {
-            const int j = x / m, i = x - j * m;
-            const double v = A[x];
-            w.T[(size_t)i * ld + 1 + j] = cmp_eps(bv[i], 0.0) < 0 ? -v : v;
-        }
-        for (int x = threadIdx.x; x < m * (m + 1); x += SX_TILE) {
-            const int i = x / (m + 1), t = x - i * (m + 1);
-            const double b = bv[i];
-            const double v = t == 0 ? b : (t - 1 == i ? 1.0 : 0.0);
-            w.T[(size_t)i * ld + (t == 0 ? 0 : n + t)] = cmp_eps(b, 0.0) < 0 ? -v : v;
-        }
-        for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j <= n + m ? 0.0 : 1.0;
-        for (int i = threadIdx.x; i < m; i += SX_TILE) w.base[i] = n + m + i;
-        __syncthreads();
-
-        long long p1 = 0, p2 = 0;
-        int status;
-        wg_update_objective(w, N1);
-        const int st1 = wg_solve(w, N1, a.max_pivots, budget, p1, s_v, s_i, &s_rv, &s_ri);
-        if (st1 == SX_PIVOT_CAP || st1 == SX_NUMERIC_FAIL || st1 == SX_EVICTED) {
-            status = st1;
-        } else if (cmp_eps(w.d[0], 0.0) < 0) {
-            status = SX_INFEASIBLE;
-        } else {
-            int art = 0;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) art |= w.base[i] >= n + m && w.base[i] < n + 2 * m;
-            status = __syncthreads_or(art) ? SX_DEGENERATE : SX_FEASIBLE;
-        }
-        if (status == SX_FEASIBLE) {
-            // phase 2: costs -c, slack costs 0, d[0] kept; canonicalise at width 1 + n + m and solve
-            for (int j = threadIdx.x; j < n; j += SX_TILE) w.d[1 + j] = -cv[j];
-            for (int j = threadIdx.x; j < m; j += SX_TILE) w.d[1 + n + j] = 0.0;
-            __syncthreads();
-            wg_update_objective(w, Ns);
-            status = wg_solve(w, Ns, a.max_pivots, budget, p2, s_v, s_i, &s_rv, &s_ri);
-        }
-        // (every path above ends behind a barrier, so T, d and base are complete here)
-        double *out = a.out + pb.out_off;
-        int *base_out = reinterpret_cast<int *>(out + m);
-        for (int i = threadIdx.x; i < m; i += SX_TILE) {
-            out[i] = w.T[(size_t)i * ld];
-            base_out[i] = w.base[i];
-        }
-        if (threadIdx.x == 0) {
-            BatchRes r;
-            r.opt = w.d[0];
-            r.p1 = p1;
-            r.p2 = p2;
-            r.status = status == SX_EVICTED ? SX_NOT_ENDED : status;
-            r.evicted = status == SX_EVICTED ? 1 : 0;
-            a.res[id] = r;
-        }
-        __syncthreads();  // the next problem overwrites the working set and s_k
-    }
-}
-
-// The device-resident entry (simplex_solve_batch_device): every problem has the launch's one shape,
-// problem k is the work counter's value, A, b and c are read in place through element strides, and
-// the epilogue writes the caller's dense result arrays -- the solution scatter and the objective
-// row included -- so nothing is left for the host.  Between the build and the epilogue the steps
-// are k_batch_solve's, statement for statement (that kernel is left exactly as it was).
-template <bool LDS>
-__global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    __shared__ double s_v[16];
-    __shared__ int s_i[16];
-    __shared__ double s_rv;
-    __shared__ int s_ri;
-    __shared__ unsigned s_k;
-    double *W;
-    if constexpr (LDS)
-        W = s_dyn;
-    else
-        W = a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    const int n = a.n, m = a.m;
+// the working set at W (sx_common.hpp BatchLay) of a problem of n variables and m constraints
+__device__ __forceinline__ BatchWork wg_carve(double *W, int n, int m) {
     const BatchLay lay = sx_batch_lay(n, m);
     BatchWork w;
     w.T = W;
@@ -297,67 +188,153 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
     w.n = n;
     w.m = m;
     w.ld = lay.ld;
-    const int ld = lay.ld, Ns = 1 + n + m, N1 = Ns + m;
+    return w;
+}
+
+// consecutive lanes walk A's faster-varying dimension
+__device__ __forceinline__ bool wg_by_col(const SxSource &src) {
+    return (src.A_sc < 0 ? -src.A_sc : src.A_sc) <= (src.A_sr < 0 ? -src.A_sr : src.A_sr);
+}
+
+// orc_build_phase1 of the problem at src: RHS, A, slack (the artificial block aliases it); a row with
+// compare(b_i) < 0 is negated across all its entries, zeros included.  Consecutive lanes walk A's
+// faster-varying dimension: the same copies and negations in either walk.  Ends behind a barrier.
+__device__ __forceinline__ void wg_build(const BatchWork &w, const SxSource &src, bool by_col) {
+    const int n = w.n, m = w.m, ld = w.ld;
+    const auto structural = [&](int i, int j) {
+        const double v = src.A[(long long)i * src.A_sr + (long long)j * src.A_sc];
+        w.T[(size_t)i * ld + 1 + j] = cmp_eps(src.b[(long long)i * src.b_si], 0.0) < 0 ? -v : v;
+    };
+    if (by_col) {
+        for (int x = threadIdx.x; x < n * m; x += SX_TILE) structural(x / n, x % n);
+    } else {
+        for (int x = threadIdx.x; x < n * m; x += SX_TILE) structural(x % m, x / m);
+    }
+    for (int x = threadIdx.x; x < m * (m + 1); x += SX_TILE) {
+        const int i = x / (m + 1), t = x - i * (m + 1);
+        const double b = src.b[(long long)i * src.b_si];
+        const double v = t == 0 ? b : (t - 1 == i ? 1.0 : 0.0);
+        w.T[(size_t)i * ld + (t == 0 ? 0 : n + t)] = cmp_eps(b, 0.0) < 0 ? -v : v;
+    }
+    for (int j = threadIdx.x; j < 1 + n + 2 * m; j += SX_TILE) w.d[j] = j <= n + m ? 0.0 : 1.0;
+    for (int i = threadIdx.x; i < m; i += SX_TILE) w.base[i] = n + m + i;
+    __syncthreads();
+}
+
+// what phase 1 decided, given its wg_solve result: SX_FEASIBLE means phase 2 follows
+__device__ __forceinline__ int wg_classify(const BatchWork &w, int st1) {
+    const int n = w.n, m = w.m;
+    if (st1 == SX_PIVOT_CAP || st1 == SX_NUMERIC_FAIL || st1 == SX_EVICTED) return st1;
+    if (cmp_eps(w.d[0], 0.0) < 0) return SX_INFEASIBLE;
+    int art = 0;
+    for (int i = threadIdx.x; i < m; i += SX_TILE) art |= w.base[i] >= n + m && w.base[i] < n + 2 * m;
+    return __syncthreads_or(art) ? SX_DEGENERATE : SX_FEASIBLE;
+}
+
+// phase 2's row: costs -c, slack costs 0, d[0] kept.  Ends behind a barrier.
+__device__ __forceinline__ void wg_phase2_costs(const BatchWork &w, const SxSource &src) {
+    for (int j = threadIdx.x; j < w.n; j += SX_TILE) w.d[1 + j] = -src.c[(long long)j * src.c_sj];
+    for (int j = threadIdx.x; j < w.m; j += SX_TILE) w.d[1 + w.n + j] = 0.0;
+    __syncthreads();
+}
+
+struct TwoPhase {
+    int status;  // SX_EVICTED included
+    bool ph2;    // phase 2 was entered: d holds its row on [0, 1 + n + m), stale phase-1 values behind it
+    long long p1, p2;
+};
+
+// orc_two_phase of the problem at src in the working set w, into the TwoPhase t; v, i, rv, ri are
+// the reduction scratch wg_solve takes.  Every path ends behind a barrier, so T, d and base are
+// complete afterwards.  Uniform over the workgroup.  Expanded in the kernel's body and not a function: the workgroup size inside the three __syncthreads_or of a problem is folded to the
+// launch's only where they reach the kernel as three separate sites.
+#define WG_TWO_PHASE(t, w, src, by_col, max_pivots, budget, v, i, rv, ri)                           \
+    do {                                                                                            \
+        const int Ns_ = 1 + (w).n + (w).m, N1_ = Ns_ + (w).m;                                       \
+        wg_build(w, src, by_col);                                                                   \
+        wg_update_objective(w, N1_);                                                                \
+        (t).p1 = (t).p2 = 0;                                                                        \
+        (t).status = wg_classify(w, wg_solve(w, N1_, max_pivots, budget, (t).p1, v, i, rv, ri));    \
+        (t).ph2 = (t).status == SX_FEASIBLE;                                                        \
+        if ((t).ph2) {                                                                              \
+            wg_phase2_costs(w, src);                                                                \
+            wg_update_objective(w, Ns_);                                                            \
+            (t).status = wg_solve(w, Ns_, max_pivots, budget, (t).p2, v, i, rv, ri);                \
+        }                                                                                           \
+    } while (0)
+
+// simplex_solve_batch: ragged problems packed by the host (A column-major, then b, then c), the RHS
+// column, the basis and a BatchRes per problem written out for the host to finish.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE) void k_batch_solve(BatchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    __shared__ double s_v[16];
+    __shared__ int s_i[16];
+    __shared__ double s_rv;
+    __shared__ int s_ri;
+    __shared__ unsigned s_k;
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    for (;;) {
+        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const unsigned k = s_k;
+        if (k >= (unsigned)a.count) return;
+        const int id = a.order[k];
+        const BatchProb pb = a.probs[id];
+        const int n = pb.n, m = pb.m;
+        const BatchWork w = wg_carve(W, n, m);
+        const double *A = a.in + pb.in_off, *bv = A + (size_t)n * m;
+        const SxSource src{A, 1, m, bv, 1, bv + m, 1};
+        const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+        TwoPhase t;
+        WG_TWO_PHASE(t, w, src, wg_by_col(src), a.max_pivots, budget, s_v, s_i, &s_rv, &s_ri);
+        double *out = a.out + pb.out_off;
+        int *base_out = reinterpret_cast<int *>(out + m);
+        for (int i = threadIdx.x; i < m; i += SX_TILE) {
+            out[i] = w.T[(size_t)i * w.ld];
+            base_out[i] = w.base[i];
+        }
+        if (threadIdx.x == 0) {
+            BatchRes r;
+            r.opt = w.d[0];
+            r.p1 = t.p1;
+            r.p2 = t.p2;
+            r.status = t.status == SX_EVICTED ? SX_NOT_ENDED : t.status;
+            r.evicted = t.status == SX_EVICTED ? 1 : 0;
+            a.res[id] = r;
+        }
+        __syncthreads();  // the next problem overwrites the working set and s_k
+    }
+}
+
+// simplex_solve_batch_device: every problem has the launch's one shape, problem k is the work
+// counter's value, A, b and c are read in place through the caller's element strides, and the
+// epilogue writes the caller's dense result arrays -- the solution scatter and the objective row
+// included -- so nothing is left for the host.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    __shared__ double s_v[16];
+    __shared__ int s_i[16];
+    __shared__ double s_rv;
+    __shared__ int s_ri;
+    __shared__ unsigned s_k;
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    const BatchWork w = wg_carve(W, n, m);
     const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
-    // consecutive lanes walk A's faster-varying dimension (uniform over the launch)
+    // wg_by_col's rule, decided once: the strides are the launch's
     const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
     for (;;) {
         if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
         __syncthreads();
         const unsigned k = s_k;
         if (k >= (unsigned)a.count) return;
-        const double *A = a.A + (long long)k * a.A_sb, *bv = a.b + (long long)k * a.b_sb;
-        const double *cv = a.c + (long long)k * a.c_sb;
-
-        // orc_build_phase1, as k_batch_solve: the same copies and negations in either walk
-        if (by_col) {
-            for (int x = threadIdx.x; x < n * m; x += SX_TILE) {
-                const int i = x / n, j = x - i * n;
-                const double v = A[(long long)i * a.A_sr + (long long)j * a.A_sc];
-                w.T[(size_t)i * ld + 1 + j] = cmp_eps(bv[(long long)i * a.b_si], 0.0) < 0 ? -v : v;
-            }
-        } else {
-            for (int x = threadIdx.x; x < n * m; x += SX_TILE) {
-                const int j = x / m, i = x - j * m;
-                const double v = A[(long long)i * a.A_sr + (long long)j * a.A_sc];
-                w.T[(size_t)i * ld + 1 + j] = cmp_eps(bv[(long long)i * a.b_si], 0.0) < 0 ? -v : v;
-            }
-        }
-        for (int x = threadIdx.x; x < m * (m + 1); x += SX_TILE) {
-            const int i = x / (m + 1), t = x - i * (m + 1);
-            const double b = bv[(long long)i * a.b_si];
-            const double v = t == 0 ? b : (t - 1 == i ? 1.0 : 0.0);
-            w.T[(size_t)i * ld + (t == 0 ? 0 : n + t)] = cmp_eps(b, 0.0) < 0 ? -v : v;
-        }
-        for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j <= n + m ? 0.0 : 1.0;
-        for (int i = threadIdx.x; i < m; i += SX_TILE) w.base[i] = n + m + i;
-        __syncthreads();
-
-        long long p1 = 0, p2 = 0;
-        int status;
-        wg_update_objective(w, N1);
-        const int st1 = wg_solve(w, N1, a.max_pivots, budget, p1, s_v, s_i, &s_rv, &s_ri);
-        if (st1 == SX_PIVOT_CAP || st1 == SX_NUMERIC_FAIL || st1 == SX_EVICTED) {
-            status = st1;
-        } else if (cmp_eps(w.d[0], 0.0) < 0) {
-            status = SX_INFEASIBLE;
-        } else {
-            int art = 0;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) art |= w.base[i] >= n + m && w.base[i] < n + 2 * m;
-            status = __syncthreads_or(art) ? SX_DEGENERATE : SX_FEASIBLE;
-        }
-        // phase 2 entered: d then holds its row on [0, 1 + n + m) and stale phase-1 values behind it
-        const bool ph2 = status == SX_FEASIBLE;
-        if (ph2) {
-            // costs -c, slack costs 0, d[0] kept; canonicalise at width 1 + n + m and solve
-            for (int j = threadIdx.x; j < n; j += SX_TILE) w.d[1 + j] = -cv[(long long)j * a.c_sj];
-            for (int j = threadIdx.x; j < m; j += SX_TILE) w.d[1 + n + j] = 0.0;
-            __syncthreads();
-            wg_update_objective(w, Ns);
-            status = wg_solve(w, Ns, a.max_pivots, budget, p2, s_v, s_i, &s_rv, &s_ri);
-        }
-        // (every path above ends behind a barrier, so T, d and base are complete here)
-        const bool feasible = status == SX_FEASIBLE, evicted = status == SX_EVICTED;
+        const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
+                           a.c + (long long)k * a.c_sb, a.c_sj};
+        TwoPhase t;
+        WG_TWO_PHASE(t, w, src, by_col, a.max_pivots, budget, s_v, s_i, &s_rv, &s_ri);
+        const bool feasible = t.status == SX_FEASIBLE, evicted = t.status == SX_EVICTED;
         if (a.x != nullptr) {
             // getSolutionHost, staged in the pivot-row copy (1 + n + m >= n doubles, free by now):
             // zeros, then x[base[i]] = T[i][0] for the basic variables, written out by consecutive lanes
@@ -366,7 +343,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
             if (feasible)
                 for (int i = threadIdx.x; i < m; i += SX_TILE) {
                     const unsigned bi = (unsigned)w.base[i];
-                    if (bi < (unsigned)n) w.prow[bi] = w.T[(size_t)i * ld];
+                    if (bi < (unsigned)n) w.prow[bi] = w.T[(size_t)i * w.ld];
                 }
             __syncthreads();
             double *x = a.x + (size_t)k * (size_t)n;
@@ -379,15 +356,15 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
         // the row simplex_last_objective_row reports: phase 2's 1 + n + m entries once phase 2 was
         // entered (what lies behind them in d is stale phase-1 data), else phase 1's full width;
         // nothing of an evicted problem
-        const int width = evicted ? 0 : ph2 ? Ns : N1;
+        const int width = evicted ? 0 : t.ph2 ? Ns : N1;
         if (a.objrow != nullptr) {
             double *row = a.objrow + (size_t)k * (size_t)N1;
             for (int j = threadIdx.x; j < N1; j += SX_TILE) row[j] = j < width ? w.d[j] : 0.0;
         }
         if (threadIdx.x == 0) {
-            a.status[k] = evicted ? SX_NOT_ENDED : status;
-            a.pivots[2 * (size_t)k] = p1;
-            a.pivots[2 * (size_t)k + 1] = p2;
+            a.status[k] = evicted ? SX_NOT_ENDED : t.status;
+            a.pivots[2 * (size_t)k] = t.p1;
+            a.pivots[2 * (size_t)k + 1] = t.p2;
             a.opt[k] = feasible ? w.d[0] : __builtin_nan("");
             if (a.row_width != nullptr) a.row_width[k] = width;
             if (evicted) atomicAdd(a.evicted, 1);
@@ -396,53 +373,46 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
     }
 }
 
+// One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
+template <class Args, void (*KL)(Args), void (*KW)(Args)>
+struct Entry {
+    static int resident(bool lds, size_t lds_bytes) {
+        static bool attr_set = false;
+        if (!attr_set) {
+            SX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       SX_BATCH_LDS_BYTES));
+            attr_set = true;
+        }
+        int device = 0, cus = 0, per_cu = 0;
+        SX_HIP(hipGetDevice(&device));
+        SX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+        SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lds ? KL : KW, SX_TILE, lds ? lds_bytes : 0));
+        if (per_cu < 1) SX_FATAL("the batch kernel does not fit a compute unit");
+        return per_cu * cus;
+    }
+    static void launch(bool lds, const Args &a, int count, int grid, size_t lds_bytes, hipStream_t s) {
+        if (grid < 1 || count < 1) return;
+        if (lds) {
+            if (lds_bytes > SX_BATCH_LDS_BYTES) SX_FATAL("batch kernel: working set exceeds the LDS class");
+            KL<<<grid, SX_TILE, lds_bytes, s>>>(a);
+        } else {
+            if (a.ws == nullptr || a.slice < 1) SX_FATAL("batch kernel: no workspace");
+            KW<<<grid, SX_TILE, 0, s>>>(a);
+        }
+        SX_HIP(hipGetLastError());
+    }
+};
+using HostEntry = Entry<BatchArgs, k_batch_solve<true>, k_batch_solve<false>>;
+using DevEntry = Entry<BatchDevArgs, k_batch_solve_dev<true>, k_batch_solve_dev<false>>;
+
 }  // namespace
 
 int sx_batch_resident(bool lds, size_t lds_bytes, bool dev) {
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[dev]) {
-        const void *fn = dev ? reinterpret_cast<const void *>(&k_batch_solve_dev<true>)
-                             : reinterpret_cast<const void *>(&k_batch_solve<true>);
-        SX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SX_BATCH_LDS_BYTES));
-        attr_set[dev] = true;
-    }
-    int device = 0, cus = 0, per_cu = 0;
-    SX_HIP(hipGetDevice(&device));
-    SX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (dev) {
-        if (lds)
-            SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve_dev<true>, SX_TILE, lds_bytes));
-        else
-            SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve_dev<false>, SX_TILE, 0));
-    } else if (lds) {
-        SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve<true>, SX_TILE, lds_bytes));
-    } else {
-        SX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_batch_solve<false>, SX_TILE, 0));
-    }
-    if (per_cu < 1) SX_FATAL("the batch kernel does not fit a compute unit");
-    return per_cu * cus;
+    return dev ? DevEntry::resident(lds, lds_bytes) : HostEntry::resident(lds, lds_bytes);
 }
-
-void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
-    if (grid < 1 || a.count < 1) return;
-    if (lds) {
-        if (lds_bytes > SX_BATCH_LDS_BYTES) SX_FATAL("batch kernel: working set exceeds the LDS class");
-        k_batch_solve_dev<true><<<grid, SX_TILE, lds_bytes, s>>>(a);
-    } else {
-        if (a.ws == nullptr || a.slice < 1) SX_FATAL("batch kernel: no workspace");
-        k_batch_solve_dev<false><<<grid, SX_TILE, 0, s>>>(a);
-    }
-    SX_HIP(hipGetLastError());
-}
-
 void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
-    if (grid < 1 || a.count < 1) return;
-    if (lds) {
-        if (lds_bytes > SX_BATCH_LDS_BYTES) SX_FATAL("batch kernel: working set exceeds the LDS class");
-        k_batch_solve<true><<<grid, SX_TILE, lds_bytes, s>>>(a);
-    } else {
-        if (a.ws == nullptr || a.slice < 1) SX_FATAL("batch kernel: no workspace");
-        k_batch_solve<false><<<grid, SX_TILE, 0, s>>>(a);
-    }
-    SX_HIP(hipGetLastError());
+    HostEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    DevEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

@@ -892,8 +892,9 @@ class Engine {
     }
 
     // ---------------------------------------------------------------- phase-1 tableau
-    // fillTableu (twoPhaseMethod.cu:145-200): each shard copies only its rows of A.  (b and c
-    // live on the primary device; the other devices' kernels read them through peer access.)
+    // fillTableu (twoPhaseMethod.cu:145-200): each shard uploads only its rows of A, a column-major
+    // slice that the strided builder reads as (A_sr, A_sc) = (1, rows).  (b and c live on the
+    // primary device; the other devices' kernels read them through peer access.)
     void build_phase1(const problem_t *P) {
         double *b_dev = dalloc<double>(m);
         SX_HIP(hipMemcpyAsync(b_dev, P->knownTermsVector, sizeof(double) * m, hipMemcpyHostToDevice, s));
@@ -906,7 +907,8 @@ class Engine {
                 SX_HIP(hipMemcpy2DAsync(A_local, sizeof(double) * x.rows, P->constraintsMatrix + x.row0,
                                         sizeof(double) * m, sizeof(double) * x.rows, n, hipMemcpyHostToDevice, x.s));
             }
-            sx_launch_build_rows(x.T, x.rows, x.row0, tl, n, m, Ns1, A_local, b_dev, x.s);
+            sx_launch_build_strided(x.T, x.rows, x.row0, tl, n, m, Ns1, SxSource{A_local, 1, x.rows, b_dev, 1, nullptr, 0},
+                                    x.s);
             sx_launch_init_vectors(x.d, N1, n, m, x.base, x.s);
             SX_HIP(hipStreamSynchronize(x.s));
             if (A_local) (void)hipFree(A_local);
@@ -917,7 +919,7 @@ class Engine {
             if (n > 0)
                 SX_HIP(hipMemcpy(c_dev, P->objectiveFunction, sizeof(double) * n, hipMemcpyHostToDevice));
         }
-        bool nonneg = true;  // no row negated (k_fill_rows negates b < -eps; b < 0 is stricter)
+        bool nonneg = true;  // no row negated (the builder negates b < -eps; b < 0 is stricter)
         for (int i = 0; i < m; ++i) nonneg = nonneg && !(P->knownTermsVector[i] < 0.0);
         set_compact(nonneg);
     }
@@ -926,18 +928,19 @@ class Engine {
     // primary device (simplex_solve_device; c null: the parity hook, no costs): every shard builds
     // its rows straight from them in one pass -- no host copy and no second device copy of A -- and
     // one int read back decides compaction by build_phase1's rule
-    void build_phase1_device(const double *A, long long A_sr, long long A_sc, const double *b, long long b_si,
-                             const double *c, long long c_sj) {
+    void build_phase1_device(SxSource src) {
         int *neg = dalloc<int>(1);
         SX_HIP(hipMemsetAsync(neg, 0, sizeof(int), s));
-        sx_launch_any_negative(b, b_si, m, neg, s);
-        if (c != nullptr) {
+        sx_launch_any_negative(src.b, src.b_si, m, neg, s);
+        if (src.c != nullptr) {
             if (!c_dev) c_dev = dalloc<double>(n);
-            sx_launch_copy_strided(c_dev, c, c_sj, n, s);
+            sx_launch_copy_strided(c_dev, src.c, src.c_sj, n, s);
         }
+        const double *A = src.A;
         for (auto &x : sh) {
             DevGuard g(x.dev);
-            sx_launch_build_strided(x.T, x.rows, x.row0, tl, n, m, Ns1, A, A_sr, A_sc, b, b_si, x.s);
+            src.A = A + (long long)x.row0 * src.A_sr;  // the shard's first row
+            sx_launch_build_strided(x.T, x.rows, x.row0, tl, n, m, Ns1, src, x.s);
             sx_launch_init_vectors(x.d, N1, n, m, x.base, x.s);
         }
         int any_neg = 0;
@@ -960,7 +963,7 @@ class Engine {
         for (auto &x : sh) {
             DevGuard g(x.dev);
             sx_launch_gen_rows(sd[2], n, m, x.row0, x.rows, lo, hi, x.T, tl, nullptr, x.s);
-            sx_launch_build_rows(x.T, x.rows, x.row0, tl, n, m, Ns1, nullptr, b_dev, x.s);
+            sx_launch_fill_generated(x.T, x.rows, x.row0, tl, n, m, Ns1, b_dev, x.s);
             sx_launch_init_vectors(x.d, N1, n, m, x.base, x.s);
         }
         sync_all();
@@ -1934,7 +1937,7 @@ int two_phase(problem_t *P, const simplex_device_solve_t *D, double *solution, d
     if (P)
         E.build_phase1(P);
     else
-        E.build_phase1_device(D->A, D->A_sr, D->A_sc, D->b, D->b_si, D->c, D->c_sj);
+        E.build_phase1_device(SxSource{D->A, D->A_sr, D->A_sc, D->b, D->b_si, D->c, D->c_sj});
     ch.stop(E.s);
     say("Phase 1: Resetting out-of-base variables");
     if (debug_on()) {
@@ -2272,13 +2275,16 @@ int twoPhaseMethodEx(problem_t *problem, double *solution, double *optimalValue,
 }
 
 // ---------------------------------------------------------------- one large LP from device arrays
-// the host-only argument checks of simplex_solve_device and its parity hook
-static int device_source_check(int n, int m, const double *A, long long A_sr, long long A_sc, const double *b,
-                               long long b_si, const double *c, long long c_sj, bool need_c) {
+// the host-only argument checks of every entry that reads a problem from device arrays (c null:
+// the parity hook, no costs; sb: the batch strides of A, b and c when there are count problems)
+static int device_source_check(int n, int m, const SxSource &src, bool need_c, int count = 1, long long A_sb = 1,
+                               long long b_sb = 1, long long c_sb = 1) {
     if (n < 1 || m < 1) return -3;
-    if (A == nullptr || b == nullptr || (need_c && c == nullptr)) return -2;
+    if (src.A == nullptr || src.b == nullptr || (need_c && src.c == nullptr)) return -2;
     // a stride of 0 would alias the elements of a dimension that has more than one
-    if ((m > 1 && (A_sr == 0 || b_si == 0)) || (n > 1 && (A_sc == 0 || (need_c && c_sj == 0)))) return -4;
+    if ((count > 1 && (A_sb == 0 || b_sb == 0 || c_sb == 0)) || (m > 1 && (src.A_sr == 0 || src.b_si == 0)) ||
+        (n > 1 && (src.A_sc == 0 || (need_c && src.c_sj == 0))))
+        return -4;
     return 0;
 }
 
@@ -2307,8 +2313,8 @@ static bool on_device(const void *p, int dev) {
 int simplex_solve_device(const simplex_device_solve_t *args, int *status_out, double *opt_out,
                          long long *pivots_out, int *row_width_out) {
     if (args == nullptr || status_out == nullptr || pivots_out == nullptr) return -1;
-    const int rc = device_source_check(args->n, args->m, args->A, args->A_sr, args->A_sc, args->b, args->b_si,
-                                       args->c, args->c_sj, true);
+    const int rc = device_source_check(
+        args->n, args->m, SxSource{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj}, true);
     if (rc != 0) return rc;
     const int dev = primary_device();
     if (!on_device(args->A, dev) || !on_device(args->b, dev) || !on_device(args->c, dev)) return -6;
@@ -2543,44 +2549,23 @@ int simplex_solve_batch_device(const simplex_batch_device_t *args) {
     const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
     if (cls == 0) return -3;
     if (count == 0) return 0;
-    if (args->A == nullptr || args->b == nullptr || args->c == nullptr || args->status == nullptr ||
-        args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr)
+    if (args->status == nullptr || args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr)
         return -2;
-    // a stride of 0 would alias the elements of a dimension that has more than one
-    if ((count > 1 && (args->A_sb == 0 || args->b_sb == 0 || args->c_sb == 0)) ||
-        (m > 1 && (args->A_sr == 0 || args->b_si == 0)) || (n > 1 && (args->A_sc == 0 || args->c_sj == 0)))
-        return -4;
+    const SxSource src{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj};
+    const int rc = device_source_check(n, m, src, true, count, args->A_sb, args->b_sb, args->c_sb);
+    if (rc != 0) return rc;
     if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0) return -5;
     const int grid = batch_device_grid(n, m, count, cls);
     const long long set = sx_batch_lay(n, m).total;
     const long long need = SX_BATCH_DEV_HEADER + (cls == 1 ? (long long)grid * set * (long long)sizeof(double) : 0);
     if (args->workspace_bytes < need) return -5;
 
-    BatchDevArgs a{};
-    a.n = n;
-    a.m = m;
-    a.count = count;
-    a.A = args->A;
-    a.A_sb = args->A_sb;
-    a.A_sr = args->A_sr;
-    a.A_sc = args->A_sc;
-    a.b = args->b;
-    a.b_sb = args->b_sb;
-    a.b_si = args->b_si;
-    a.c = args->c;
-    a.c_sb = args->c_sb;
-    a.c_sj = args->c_sj;
-    a.max_pivots = args->max_pivots;
-    a.budget = g_batch_budget;
-    a.status = args->status;
-    a.pivots = args->pivots;
-    a.opt = args->opt;
-    a.x = args->x;
-    a.base = args->base;
-    a.objrow = args->objrow;
-    a.row_width = args->row_width;
-    a.evicted = args->evicted;
-    a.counter = static_cast<unsigned *>(args->workspace);
+    // in the struct's order, which is the caller's; ws and slice stay zero for the LDS class
+    BatchDevArgs a{n, m, count,
+                   args->A, args->A_sb, args->A_sr, args->A_sc, args->b, args->b_sb, args->b_si, args->c, args->c_sb, args->c_sj,
+                   args->max_pivots, g_batch_budget,
+                   args->status, args->pivots, args->opt, args->x, args->base, args->objrow, args->row_width, args->evicted,
+                   static_cast<unsigned *>(args->workspace)};
     if (cls == 1) {
         a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
         a.slice = set;
@@ -3109,7 +3094,8 @@ int simplex_dev_build_phase1(problem_t *problem, double *T, long long ld, double
 
 int simplex_dev_build_phase1_device(int n, int m, const double *A, long long A_sr, long long A_sc, const double *b,
                                     long long b_si, double *T, long long ld, double *d, int *base) {
-    const int rc = device_source_check(n, m, A, A_sr, A_sc, b, b_si, nullptr, 0, false);
+    const SxSource src{A, A_sr, A_sc, b, b_si, nullptr, 0};
+    const int rc = device_source_check(n, m, src, false);
     if (rc != 0) return rc;
     const int dev = primary_device();
     if (!on_device(A, dev) || !on_device(b, dev)) return -6;
@@ -3118,7 +3104,7 @@ int simplex_dev_build_phase1_device(int n, int m, const double *A, long long A_s
         SX_HIP(hipStreamSynchronize(nullptr));
     }
     Engine E(n, m);
-    E.build_phase1_device(A, A_sr, A_sc, b, b_si, nullptr, 0);
+    E.build_phase1_device(src);
     E.download(T, (size_t)ld, E.N1, d);
     E.read_base(base);
     return 0;

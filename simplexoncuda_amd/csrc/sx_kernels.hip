@@ -3246,41 +3246,24 @@ __global__ void k_gemv_apply(double *d, Cols c, const double *__restrict__ parti
 
 // ---------------------------------------------------------------------------------------
 // Tableau construction (fillTableu + checkColumns, twoPhaseMethod.cu:145-200, 86-111).
-// A_local is the shard's slice of the column-major A: A_local[j*rows + i] = A(row0+i, j).
-// 32x32 LDS transpose so both the read (along i) and the write (along j) are coalesced.
-__global__ __launch_bounds__(256) void k_fill_structural(double *T, int rows, TLay tl, int n,
-                                                         const double *__restrict__ A_local) {
-    __shared__ double tile[32][33];
-    const int i_base = blockIdx.x * 32, j_base = blockIdx.y * 32;
-    for (int jj = threadIdx.y; jj < 32; jj += 8) {
-        const int i = i_base + threadIdx.x, j = j_base + jj;
-        tile[jj][threadIdx.x] = (i < rows && j < n) ? A_local[(size_t)j * rows + i] : 0.0;
-    }
-    __syncthreads();
-    for (int ii = threadIdx.y; ii < 32; ii += 8) {
-        const int i = i_base + ii, j = j_base + threadIdx.x;
-        if (i < rows && j < n) T[tl.idx(i, 1 + j)] = tile[threadIdx.x][ii];
-    }
+// Stored column j of global row gi of the phase-1 tableau, given b_i and -- for a structural
+// column 1 <= j <= n -- its value a = A(gi, j - 1): the RHS, A, the slack (and, stored without
+// aliasing, artificial) identities, and the b<0 quirk: a row with compare(b_i) < 0 is negated
+// across ALL its entries, slack and artificial included, so its zeros become -0.0.
+__device__ __forceinline__ double phase1_entry(int gi, int j, int n, int m, double bi, double a) {
+    const double x = j == 0 ? bi : j <= n ? a : (j == 1 + n + gi || j == 1 + n + m + gi) ? 1.0 : 0.0;
+    return cmp_eps(bi, 0.0) < 0 ? -x : x;
 }
 
-// RHS, slack/artificial identities, and the b<0 quirk: a row with compare(b_i) < 0 is
-// negated across ALL its entries, slack and artificial included.
+// The generator path's filler: everything around structural columns that are already in T.
 __global__ void k_fill_rows(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const double *b_full) {
     const int i = blockIdx.y;
     if (i >= rows) return;
     const int gi = row0 + i;
     const double bi = b_full[gi];
-    const bool neg = cmp_eps(bi, 0.0) < 0;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < Ns; j += gridDim.x * blockDim.x) {
         double &el = T[tl.idx(i, j)];
-        double x;
-        if (j == 0)
-            x = bi;
-        else if (j <= n)
-            x = el;
-        else
-            x = (j == 1 + n + gi || j == 1 + n + m + gi) ? 1.0 : 0.0;
-        el = neg ? -x : x;
+        el = phase1_entry(gi, j, n, m, bi, j >= 1 && j <= n ? el : 0.0);
     }
 }
 
@@ -3292,17 +3275,17 @@ __global__ void k_init_vectors(double *d, int N1, int n, int m, int *base) {
     if (t < m) base[t] = n + m + t;
 }
 
-// The whole phase-1 tableau of a shard -- k_fill_structural and k_fill_rows in one pass -- straight
-// from a caller's device arrays read through element strides (simplex_solve_device): stored
-// column 0 = b, 1 + j = A(:, j), then the slack (and, without aliasing, artificial) identities,
-// the row negated where compare(b_i) < 0 exactly as k_fill_rows does (its zeros become -0.0).
+// The whole phase-1 tableau of a shard in one pass, straight from device arrays read through
+// element strides: a caller's (simplex_solve_device) or the shard's uploaded column-major slice of
+// a host problem (A_sr = 1, A_sc = rows).  A is indexed by the row within the shard (src.A is the
+// shard's first row), b and the identity columns by the global row.
 // One block builds a 16-row strip x SX_BUILD_COLS stored columns.  Tiles that hold structural
 // columns are staged through a padded LDS tile so that both sides move whole lines: consecutive
 // lanes walk the source along its smaller stride (walk_i, uniform over the launch: along i for a
-// transposed view, else along j), and the write is consecutive 16-byte stores -- in the blocked
-// layout a strip's column range is one contiguous run of 4x4 blocks, so lane k stores the pair at
-// offset 2k of that run (TLay::idx only names the address; jB and SX_BUILD_COLS keep a tile inside
-// one region).  Tiles behind the structural columns store their identity values directly.
+// column-major or transposed source, else along j), and the write is consecutive 16-byte stores --
+// in the blocked layout a strip's column range is one contiguous run of 4x4 blocks, so lane k stores
+// the pair at offset 2k of that run (TLay::idx only names the address; jB and SX_BUILD_COLS keep a
+// tile inside one region).  Tiles behind the structural columns store their identity values directly.
 #define SX_BUILD_COLS 256
 __global__ __launch_bounds__(256) void k_build_strided(double *__restrict__ T, int rows, int row0, TLay tl, int n, int m,
                                                        int Ns, const double *__restrict__ A, long long A_sr,
@@ -3317,16 +3300,8 @@ __global__ __launch_bounds__(256) void k_build_strided(double *__restrict__ T, i
     __syncthreads();
     // stored column j < Ns of the strip's row r < nr
     auto value = [&](int r, int j) -> double {
-        const int gi = row0 + i0 + r;
-        const double bi = sb[r];
-        double x;
-        if (j == 0)
-            x = bi;
-        else if (j <= n)
-            x = A[(long long)gi * A_sr + (long long)(j - 1) * A_sc];
-        else
-            x = (j == 1 + n + gi || j == 1 + n + m + gi) ? 1.0 : 0.0;
-        return cmp_eps(bi, 0.0) < 0 ? -x : x;
+        const double a = j >= 1 && j <= n ? A[(long long)(i0 + r) * A_sr + (long long)(j - 1) * A_sc] : 0.0;
+        return phase1_entry(row0 + i0 + r, j, n, m, sb[r], a);
     };
     const bool staged = j0 <= n;  // (uniform over the block)
     if (staged) {
@@ -3794,26 +3769,23 @@ void sx_launch_gemv_apply(double *d, Cols c, const double *partials, int nblk, h
     k_gemv_apply<<<(c.N + 255) / 256, 256, 0, s>>>(d, c, partials, nblk);
 }
 
-void sx_launch_build_rows(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const double *A_local,
-                          const double *b_full, hipStream_t s) {
+void sx_launch_fill_generated(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const double *b_full,
+                              hipStream_t s) {
     if (rows <= 0) return;
-    dim3 tb(32, 8);
-    dim3 tg((rows + 31) / 32, (n + 31) / 32);
-    // A_local == nullptr: the structural columns are already in T (device generator)
-    if (n > 0 && A_local != nullptr) k_fill_structural<<<tg, tb, 0, s>>>(T, rows, tl, n, A_local);
     int gx = (Ns + 255) / 256;
     if (gx > 64) gx = 64;
     dim3 rg(gx, rows);
     k_fill_rows<<<rg, 256, 0, s>>>(T, rows, row0, tl, n, m, Ns, b_full);
 }
 
-void sx_launch_build_strided(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const double *A,
-                             long long A_sr, long long A_sc, const double *b, long long b_si, hipStream_t s) {
+void sx_launch_build_strided(double *T, int rows, int row0, TLay tl, int n, int m, int Ns, const SxSource &src,
+                             hipStream_t s) {
     if (rows <= 0) return;
     if (tl.jB < Ns && tl.jB % SX_BUILD_COLS != 0) SX_FATAL("region boundary inside a build tile");
-    const int walk_i = std::llabs(A_sc) > std::llabs(A_sr) ? 1 : 0;
+    const int walk_i = std::llabs(src.A_sc) > std::llabs(src.A_sr) ? 1 : 0;
     dim3 grid((Ns + SX_BUILD_COLS - 1) / SX_BUILD_COLS, (rows + 15) / 16);
-    k_build_strided<<<grid, 256, 0, s>>>(T, rows, row0, tl, n, m, Ns, A, A_sr, A_sc, b, b_si, walk_i);
+    k_build_strided<<<grid, 256, 0, s>>>(T, rows, row0, tl, n, m, Ns, src.A, src.A_sr, src.A_sc, src.b, src.b_si,
+                                         walk_i);
 }
 
 void sx_launch_copy_strided(double *dst, const double *src, long long stride, int count, hipStream_t s) {
