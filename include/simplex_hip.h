@@ -19,7 +19,8 @@ extern "C" {
 #define SIMPLEX_PIVOT_CAP -11    /* opt-in pivot budget reached */
 #define SIMPLEX_NUMERIC_FAIL -12 /* eligible pivot but the ratio argmin found no row */
 #define SIMPLEX_HANG -13         /* fused batch: an in-kernel hand-off timed out (never expected) */
-#define SIMPLEX_MAX_GPUS 8        /* shards (GPUs) one solve can use: simplex_set_gpus, SIMPLEX_GPUS, --gpus */
+#define SIMPLEX_BAD_SHAPE -14    /* ragged device batch: a problem's dimensions lie outside the envelope */
+#define SIMPLEX_MAX_GPUS 8       /* shards (GPUs) one solve can use: simplex_set_gpus, SIMPLEX_GPUS, --gpus */
 
 /* ---- configuration ---- */
 int simplex_version(void);
@@ -229,6 +230,36 @@ long long simplex_batch_device_workspace(int n, int m, int count);
  * -2 a required pointer is NULL (A, b, c, status, pivots, opt, evicted), -4 a stride of 0 on a
  * dimension longer than 1, -5 workspace NULL, misaligned or too small */
 int simplex_solve_batch_device(const simplex_batch_device_t *args);
+
+/* ---- ragged device batch: per-problem shapes inside one padded envelope ---- */
+/* simplex_solve_batch_device with args->n x args->m as an ENVELOPE: the input and output arrays keep
+ * its shapes and strides, and problem k is the LP on the leading block A[k][0..m_k[k])[0..n_k[k]),
+ * b[k][0..m_k[k]), c[k][0..n_k[k]).  n_k and m_k are int arrays of count entries in device memory.
+ * No element outside a problem's block is read (the padding may hold anything), and problem k gets
+ * twoPhaseMethodEx's result for that n_k[k] x m_k[k] problem, bit for bit; solving a zero-padded
+ * problem instead does not give it.  max_pivots, the resident budget (by default that of the
+ * problem's own shape) and eviction work as in simplex_solve_batch_device.
+ * Outputs, in the envelope's dense shapes: x[k][n_k[k]..n) is +0.0; base[k][m_k[k]..m) is -1, and
+ * base[k][i] is in the problem's own numbering (< n_k structural, n_k + i slack, n_k + m_k + i
+ * artificial); objrow[k] is laid out in ENVELOPE columns -- [0] the objective, [1 + j] the structural
+ * entry j < n_k, [1 + n + i] the slack entry (the dual y_i) i < m_k, [1 + n + m + i] the artificial
+ * entry i < m_k when phase 1 ended the solve, +0.0 everywhere else -- so column arithmetic on the
+ * envelope's n and m holds for every problem; row_width[k] stays the problem's own logical width
+ * (1+n_k+m_k, 1+n_k+2m_k, or 0 when evicted).  With n_k[k] == n and m_k[k] == m everything is
+ * simplex_solve_batch_device's.
+ * The host cannot see the dimensions without a synchronisation, so the kernel tests them before it
+ * indexes anything with them: n_k[k] < 1, m_k[k] < 1, n_k[k] > n or m_k[k] > m gives problem k the
+ * status SIMPLEX_BAD_SHAPE, pivots 0, opt NaN, x zero, base -1, a zero row and row_width 0; the other
+ * problems of the call are not affected.
+ * order (device, count ints) or NULL: the j-th problem a workgroup takes from the work counter is
+ * order[j] (NULL: j).  Larger problems first keep the long ones out of the tail.  It must be a
+ * permutation of 0..count-1 (the caller's contract); an entry outside that range is skipped, and
+ * results do not depend on the order.
+ * The workspace is simplex_batch_device_workspace(n, m, count) bytes, the envelope's.  Returns
+ * simplex_solve_batch_device's codes, -2 also for a NULL n_k or m_k.  Like that entry the call only
+ * enqueues two small memsets and one launch on `stream`. */
+int simplex_solve_batch_device_ragged(const simplex_batch_device_t *args, const int *n_k, const int *m_k,
+                                      const int *order /* or NULL */);
 
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through

@@ -7,9 +7,13 @@ median of several repeats), and a 64-problem subset of the same instances with a
 twoPhaseMethodEx, the one-problem entry point.  The same instances, stacked once into device
 tensors, are also solved with solve_batch_tensors (default arguments, and objective_row=True): the
 same host clock, each call followed by torch.cuda.synchronize(), the three batched paths taking
-turns inside every repeat.  The rates are printed and written to profiles/batch_bench.txt (or --out).
+turns inside every repeat.  The ragged leg (ragged_leg below) then times the ragged device entry
+against the one-shape entry on the same uniform instances, and against solve_batch on problems whose
+dimensions vary inside a 64 x 64 envelope.  The rates are printed and written to
+profiles/batch_bench.txt (or --out).
 
-    python scripts/batch_bench.py [--problems 1024] [--subset 64] [--repeats 7] [--out FILE]
+    python scripts/batch_bench.py [--problems 1024] [--subset 64] [--repeats 7] [--legs all|uniform|ragged]
+                                  [--out FILE]
 """
 import argparse
 import os
@@ -54,18 +58,127 @@ def device_tensors(probs):
     return tuple(torch.from_numpy(np.stack([a[k] for a in arrays])).cuda() for k in range(3))
 
 
+def seconds_in_turn(fns, repeats):
+    """every time of several functions timed one after the other inside every repeat"""
+    times = [[] for _ in fns]
+    for _ in range(repeats):
+        for ts, fn in zip(times, fns):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+    return times
+
+
+def ragged_leg(args):
+    """The ragged device entry (solve_batch_tensors(n_active=, m_active=)), two questions.
+
+    Cost of raggedness: the SHAPES' instances with every block fully active, the ragged entry (default
+    order, and order=False) and the one-shape entry taking turns inside every repeat; the yardstick
+    is the one-shape entry of the same run, whose own spread (min and max of its repeats) is printed.
+
+    The use case: as many LPs with n_k and m_k drawn uniformly from 8..64, in a (64, 64) envelope,
+    through the ragged entry (default order, order=False) and through the host path solve_batch on
+    the same problems, after asserting that status, pivots and objective agree on every instance;
+    and a batch of small problems whose few large ones come last, the case the order exists for."""
+    ms = lambda t: f"{statistics.median(t) * 1e3:.3f}"  # noqa: E731
+    lines = ["# ragged, uniform dims: n m problems one_shape_ms one_shape_min_ms one_shape_max_ms ragged_ms "
+             "ragged_order_false_ms ragged_over_one_shape"]
+    for n, m in SHAPES:
+        probs = [sx.generateRandomProblem(n, m, 7919 * k + n * 100 + m, 1, 100) for k in range(args.problems)]
+        A, b, c = device_tensors(probs)
+        for p in probs:
+            p.close()
+        n_k = torch.full((len(probs),), n, dtype=torch.int32, device="cuda")
+        m_k = torch.full((len(probs),), m, dtype=torch.int32, device="cuda")
+        one = sx.solve_batch_tensors(A, b, c, objective_row=True)
+        rag = sx.solve_batch_tensors(A, b, c, objective_row=True, n_active=n_k, m_active=m_k)
+        for f in ("status", "pivots", "base", "row_width"):
+            assert torch.equal(getattr(one, f), getattr(rag, f)), f
+        for f in ("optimal_value", "solution", "objective_row"):
+            assert torch.equal(getattr(one, f).view(torch.int64), getattr(rag, f).view(torch.int64)), f
+
+        def call(**kw):
+            sx.solve_batch_tensors(A, b, c, **kw)
+            torch.cuda.synchronize()
+
+        fns = [lambda: call(), lambda: call(n_active=n_k, m_active=m_k),
+               lambda: call(n_active=n_k, m_active=m_k, order=False)]
+        seconds_in_turn(fns, 2)  # warm-up
+        t_one, t_rag, t_raw = seconds_in_turn(fns, args.repeats)
+        line = (f"{n} {m} {len(probs)} {ms(t_one)} {min(t_one) * 1e3:.3f} {max(t_one) * 1e3:.3f} {ms(t_rag)} {ms(t_raw)} "
+                f"{statistics.median(t_rag) / statistics.median(t_one):.3f}")
+        print(line, flush=True)
+        lines.append(line)
+
+    lines.append("# ragged, dims inside a 64 x 64 envelope (uniform: n_k, m_k uniform in 8..64; tail: 8..16 but for the last "
+                 "sixteenth of the batch, 56..64): draw problems solve_batch_ms ragged_ms solve_batch_ms_over_ragged_ms | "
+                 "in turn: ragged_default_order_ms ragged_order_false_ms ragged_order_given_ms")
+    rng = np.random.default_rng(64)
+    uniform = rng.integers(8, 65, size=(args.problems, 2))
+    tail = np.concatenate([rng.integers(8, 17, size=(args.problems - args.problems // 16, 2)),
+                           rng.integers(56, 65, size=(args.problems // 16, 2))])
+    for draw, dims in (("uniform", uniform), ("tail", tail)):
+        line = f"{draw} " + mixed_dims_case(args, dims, 64, 64)
+        print(line, flush=True)
+        lines.append(line)
+    return lines
+
+
+def mixed_dims_case(args, dims, n, m):
+    """problems of the given (n_k, m_k) in an n x m envelope whose padding is NaN: solve_batch on the
+    host problems and the ragged entry in turn; then the ragged entry with its default order (built
+    inside the call), with order=False and with the same larger-first order passed in, in turn"""
+    probs = [sx.generateRandomProblem(int(nk), int(mk), 7919 * k + int(nk) * 100 + int(mk), 1, 100)
+             for k, (nk, mk) in enumerate(dims)]
+    Ae, be, ce = (np.full(s, np.nan) for s in ((len(probs), m, n), (len(probs), m), (len(probs), n)))
+    for k, p in enumerate(probs):
+        Ak, bk, ck = p.arrays()
+        Ae[k, :p.m, :p.n], be[k, :p.m], ce[k, :p.n] = Ak, bk, ck
+    A, b, c = (torch.from_numpy(t).cuda() for t in (Ae, be, ce))
+    n_k = torch.from_numpy(dims[:, 0].astype(np.int32)).cuda()
+    m_k = torch.from_numpy(dims[:, 1].astype(np.int32)).cuda()
+    got = sx.solve_batch(probs)
+    rag = sx.solve_batch_tensors(A, b, c, n_active=n_k, m_active=m_k)
+    assert rag.evicted == 0
+    status, pivots, opt = rag.status.cpu().numpy(), rag.pivots.cpu().numpy(), rag.optimal_value.cpu().numpy()
+    for k, g in enumerate(got):
+        assert (g.status, tuple(g.pivots)) == (int(status[k]), tuple(int(v) for v in pivots[k])), k
+        assert g.status != sx.FEASIBLE or g.optimal_value == opt[k], k
+
+    def call(**kw):
+        sx.solve_batch_tensors(A, b, c, n_active=n_k, m_active=m_k, **kw)
+        torch.cuda.synchronize()
+
+    # the host path against the ragged call that follows it, then the three orders among themselves (a call
+    # right behind the host-heavy solve_batch is slower than the same call behind a tensor call)
+    fns = [lambda: sx.solve_batch(probs), lambda: call()]
+    seconds_in_turn(fns, 2)  # warm-up
+    t_host, t_rag = (statistics.median(t) for t in seconds_in_turn(fns, args.repeats))
+    given = sx.api._default_ragged_order(n_k, m_k)
+    fns = [lambda: call(), lambda: call(order=False), lambda: call(order=given)]
+    seconds_in_turn(fns, 2)  # warm-up
+    t_def, t_raw, t_giv = (statistics.median(t) for t in seconds_in_turn(fns, args.repeats))
+    for p in probs:
+        p.close()
+    return (f"{len(probs)} {t_host * 1e3:.3f} {t_rag * 1e3:.3f} {t_host / t_rag:.1f} "
+            f"{t_def * 1e3:.3f} {t_raw * 1e3:.3f} {t_giv * 1e3:.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--problems", type=int, default=1024)
     ap.add_argument("--subset", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--legs", choices=["all", "uniform", "ragged"], default="all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.txt"))
     args = ap.parse_args()
 
-    lines = [f"# scripts/batch_bench.py --problems {args.problems} --subset {args.subset} --repeats {args.repeats}",
-             "# n m problems class batch_LPs_per_s loop_LPs_per_s ratio batch_ms loop_ms_per_LP "
-             "tensors_ms tensors_row_ms batch_ms_over_tensors_ms"]
-    for n, m in SHAPES:
+    lines = [f"# scripts/batch_bench.py --problems {args.problems} --subset {args.subset} --repeats {args.repeats}"
+             + ("" if args.legs == "all" else f" --legs {args.legs}")]
+    if args.legs != "ragged":
+        lines.append("# n m problems class batch_LPs_per_s loop_LPs_per_s ratio batch_ms loop_ms_per_LP "
+                     "tensors_ms tensors_row_ms batch_ms_over_tensors_ms")
+    for n, m in SHAPES if args.legs != "ragged" else []:
         probs = [sx.generateRandomProblem(n, m, 7919 * k + n * 100 + m, 1, 100) for k in range(args.problems)]
         subset = probs[:args.subset]
         # the two paths agree on the subset (and this warms both up)
@@ -98,6 +211,8 @@ def main():
         lines.append(line)
         for p in probs:
             p.close()
+    if args.legs != "uniform":
+        lines += ragged_leg(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")

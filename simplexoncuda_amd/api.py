@@ -20,10 +20,11 @@ NOT_ENDED = -10
 PIVOT_CAP = -11
 NUMERIC_FAIL = -12
 HANG = -13
+BAD_SHAPE = -14
 
 STATUS_NAMES = {FEASIBLE: "FEASIBLE", INFEASIBLE: "INFEASIBLE", UNBOUNDED: "UNBOUNDED",
                 DEGENERATE: "DEGENERATE", NOT_ENDED: "NOT_ENDED", PIVOT_CAP: "PIVOT_CAP",
-                NUMERIC_FAIL: "NUMERIC_FAIL", HANG: "HANG"}
+                NUMERIC_FAIL: "NUMERIC_FAIL", HANG: "HANG", BAD_SHAPE: "BAD_SHAPE"}
 
 RAND_MSVC = 0
 RAND_GLIBC = 1
@@ -209,7 +210,15 @@ def solve_batch(problems, max_pivots=-1):
 class BatchTensors:
     """solve_batch_tensors' results: device tensors, one row per problem.  For a problem that is not
     FEASIBLE optimal_value is NaN and its solution row is zero; objective_row (when asked for) holds
-    row_width[k] entries of problem k's final objective row, zero-padded to 1 + n + 2m."""
+    row_width[k] entries of problem k's final objective row, zero-padded to 1 + n + 2m.
+
+    After a ragged call (n_active / m_active are the per-problem dimensions, else None) n and m are
+    the envelope's: solution[k, n_k:] is zero, base[k, m_k:] is -1 and base[k, :m_k] is in problem
+    k's own numbering; objective_row[k] is laid out in envelope columns -- [0], the structural entries
+    at [1 + j], the slack entries at [1 + n + i], the artificial entries (when phase 1 ended the
+    solve) at [1 + n + m + i], zero elsewhere -- so reduced_costs and duals are the same views, and
+    row_width[k] is the problem's own logical width.  A problem whose dimensions lie outside the
+    envelope has status BAD_SHAPE and cleared outputs."""
     status: object         # int32 [B]
     pivots: object         # int64 [B, 2]: phase 1, phase 2
     optimal_value: object  # float64 [B]
@@ -218,6 +227,8 @@ class BatchTensors:
     objective_row: object  # float64 [B, 1 + n + 2m], or None
     row_width: object      # int32 [B], or None
     evicted: object        # int; the device tensor (int32 [1]) with finish=False
+    n_active: object = None  # int32 [B] after a ragged call
+    m_active: object = None  # int32 [B] after a ragged call
 
     @property
     def reduced_costs(self):
@@ -232,7 +243,31 @@ class BatchTensors:
         return self.objective_row[:, 1 + n:1 + n + m]
 
 
-def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True):
+def _check_ragged_arg(name, t, B, device):
+    """a per-problem int32 [B] tensor on the inputs' device; checked on the host, no device use"""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"solve_batch_tensors: {name} must be a torch.Tensor, not {type(t).__name__}")
+    if t.dtype != torch.int32:
+        raise TypeError(f"solve_batch_tensors: {name} must be int32, not {t.dtype}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"solve_batch_tensors: {name} must be [{B}], one entry per problem; got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"solve_batch_tensors: {name} is on {t.device}; it must be on A's device, {device}")
+
+
+def _default_ragged_order(n_active, m_active):
+    """Larger problems first, so the long ones do not form the launch's tail: a stable descending
+    argsort of the tableau size m_k (1 + n_k + m_k), on the tensors' device, without a sync."""
+    import torch
+
+    n_k, m_k = n_active.to(torch.int64), m_active.to(torch.int64)
+    return torch.argsort(m_k * (1 + n_k + m_k), descending=True, stable=True).to(torch.int32)
+
+
+def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True, n_active=None, m_active=None,
+                        order=None):
     """twoPhaseMethodEx of B problems of one shape held in device tensors (simplex_solve_batch_device):
     A [B, m, n], b [B, m], c [B, n], float64 on one ROCm device, read in place through their strides
     (a transposed or sliced view is not copied).  One launch on torch's current stream of that device
@@ -243,7 +278,16 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     waits for the stream) and re-solves such problems through twoPhaseMethodEx, so every result is
     twoPhaseMethodEx's whatever the budget; finish=False returns right after the enqueue, without
     synchronising, and `evicted` is the device tensor.  Shapes with batch_class(n, m) == 0 are
-    refused: solve_batch takes those."""
+    refused: solve_batch takes those.
+
+    Ragged batches (simplex_solve_batch_device_ragged): with n_active and / or m_active, int32 [B]
+    tensors on A's device, [m, n] is a padded envelope and problem k is the LP on
+    A[k, :m_active[k], :n_active[k]], b[k, :m_active[k]], c[k, :n_active[k]] (one of the two left
+    None: the envelope's).  The padding is never read, and problem k gets twoPhaseMethodEx's result
+    for its own shape, in the conventions BatchTensors describes; dimensions outside the envelope
+    give that problem BAD_SHAPE.  order: an int32 [B] permutation on A's device in which the
+    workgroups take the problems; None builds larger-first on the device (no sync), False is 0..B-1.
+    Results do not depend on it."""
     import torch
 
     B, m, n = _check_device_shapes("solve_batch_tensors", A, b, c, batch=True)
@@ -252,6 +296,15 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     if n < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
         raise ValueError(f"solve_batch_tensors: a problem of {n} variables x {m} constraints is not solved by a "
                          "resident workgroup; use solve_batch for such shapes")
+    ragged = n_active is not None or m_active is not None
+    if ragged:
+        for name, t in (("n_active", n_active), ("m_active", m_active)):
+            if t is not None:
+                _check_ragged_arg(name, t, B, A.device)
+        if order is not None and order is not False:
+            _check_ragged_arg("order", order, B, A.device)
+    elif order is not None and order is not False:
+        raise ValueError("solve_batch_tensors: order belongs to a ragged call (n_active, m_active)")
     _check_device_placement("solve_batch_tensors", A, b, c)
     lib = _lib.load()
     dev = A.device
@@ -265,6 +318,13 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
         row = torch.empty((B, N1), dtype=torch.float64, device=dev) if objective_row else None
         width = torch.empty(B, dtype=torch.int32, device=dev) if objective_row else None
         evicted = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int32, device=dev)  # (the call zeroes it)
+        if ragged:
+            n_active = torch.full((B,), n, dtype=torch.int32, device=dev) if n_active is None else n_active.contiguous()
+            m_active = torch.full((B,), m, dtype=torch.int32, device=dev) if m_active is None else m_active.contiguous()
+            if order is None:
+                order = _default_ragged_order(n_active, m_active)
+            elif order is not False:
+                order = order.contiguous()
         if B > 0:
             ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
             if ws_bytes < 0:
@@ -281,10 +341,17 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
                 row_width=width.data_ptr() if objective_row else None, evicted=evicted.data_ptr(),
                 workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
                 stream=torch.cuda.current_stream(dev).cuda_stream)
-            rc = lib.simplex_solve_batch_device(ctypes.byref(args))
-            if rc < 0:
-                raise ValueError(f"simplex_solve_batch_device: bad arguments ({rc})")
-        out = BatchTensors(status, pivots, opt, x, base, row, width, evicted)
+            if ragged:
+                rc = lib.simplex_solve_batch_device_ragged(ctypes.byref(args), n_active.data_ptr(), m_active.data_ptr(),
+                                                           None if order is False else order.data_ptr())
+                if rc < 0:
+                    raise ValueError(f"simplex_solve_batch_device_ragged: bad arguments ({rc})")
+            else:
+                rc = lib.simplex_solve_batch_device(ctypes.byref(args))
+                if rc < 0:
+                    raise ValueError(f"simplex_solve_batch_device: bad arguments ({rc})")
+        out = BatchTensors(status, pivots, opt, x, base, row, width, evicted,
+                           n_active if ragged else None, m_active if ragged else None)
         if not finish:
             return out
         out.evicted = int(evicted.item()) if B > 0 else 0
@@ -295,13 +362,17 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
 
 def _finish_evicted(out, A, b, c, max_pivots):
     """Re-solve the problems the kernel left NOT_ENDED through twoPhaseMethodEx and write their
-    results into the output tensors in the kernel's conventions."""
+    results into the output tensors in the kernel's conventions (a ragged call: the problem's active
+    block, the envelope's padding and row layout)."""
     import torch
 
     dev = out.status.device
-    n = out.solution.shape[1]
-    for k in torch.nonzero(out.status == NOT_ENDED).flatten().tolist():
-        p = Problem.from_arrays(A[k].cpu().numpy(), b[k].cpu().numpy(), c[k].cpu().numpy())
+    n, m = out.solution.shape[1], out.base.shape[1]
+    left = torch.nonzero(out.status == NOT_ENDED).flatten().tolist()
+    ragged = out.n_active is not None
+    dims = [(n, m)] * len(left) if not ragged else list(zip(out.n_active[left].tolist(), out.m_active[left].tolist()))
+    for k, (nk, mk) in zip(left, dims):
+        p = Problem.from_arrays(A[k, :mk, :nk].cpu().numpy(), b[k, :mk].cpu().numpy(), c[k, :nk].cpu().numpy())
         try:
             r = twoPhaseMethodEx(p, max_pivots)
             d = last_objective_row()
@@ -310,12 +381,19 @@ def _finish_evicted(out, A, b, c, max_pivots):
         feasible = r.status == FEASIBLE
         out.status[k] = r.status
         out.pivots[k] = torch.tensor(r.pivots, dtype=torch.int64, device=dev)
-        out.base[k] = torch.from_numpy(r.base).to(dev)
+        out.base[k] = torch.from_numpy(np.concatenate([r.base, np.full(m - mk, -1, dtype=np.int32)])).to(dev)
         out.optimal_value[k] = r.optimal_value if feasible else float("nan")
-        out.solution[k] = torch.from_numpy(r.solution if feasible else np.zeros(n)).to(dev)
+        xk = np.zeros(n)
+        if feasible:
+            xk[:nk] = r.solution
+        out.solution[k] = torch.from_numpy(xk).to(dev)
         if out.objective_row is not None:
-            out.objective_row[k].zero_()
-            out.objective_row[k, :len(d)] = torch.from_numpy(d).to(dev)
+            # the problem's logical columns [0, 1 + nk) | slacks | artificials -> the envelope's
+            e = np.zeros(1 + n + 2 * m)
+            e[:1 + nk] = d[:1 + nk]
+            e[1 + n:1 + n + mk] = d[1 + nk:1 + nk + mk]
+            e[1 + n + m:1 + n + m + len(d) - (1 + nk + mk)] = d[1 + nk + mk:]
+            out.objective_row[k] = torch.from_numpy(e).to(dev)
             out.row_width[k] = len(d)
 
 

@@ -15,10 +15,12 @@
 // j >= 1 + n + m reads stored column j - m; d keeps the full width.
 //
 // The two-phase method is written once (WG_TWO_PHASE and its parts), over a strided source (sx_common.hpp
-// SxSource).  Its two entries differ only in where a problem comes from and where its results go:
+// SxSource).  Its entries differ only in where a problem comes from and where its results go:
 // k_batch_solve (simplex_solve_batch: ragged problems packed by the host -- column-major A, the
-// source with A_sr = 1, A_sc = m -- results finished on the host) and k_batch_solve_dev
-// (simplex_solve_batch_device: one shape, the caller's strides, every result written by the kernel).
+// source with A_sr = 1, A_sc = m -- results finished on the host), k_batch_solve_dev
+// (simplex_solve_batch_device: one shape, the caller's strides, every result written by the kernel)
+// and k_batch_solve_rag (simplex_solve_batch_device_ragged: the same with per-problem dimensions
+// inside one envelope shape).
 
 #include <float.h>
 
@@ -373,6 +375,95 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
     }
 }
 
+// simplex_solve_batch_device_ragged: k_batch_solve_dev's strided source and on-device epilogue with
+// k_batch_solve's per-problem carve.  a.n x a.m is the envelope that shapes every input and output
+// array; problem k is the n_k[k] x m_k[k] leading block of its slot, and only that block is read.
+// The dimensions are tested before anything is indexed with them; a problem that fails gets
+// SX_BAD_SHAPE and cleared outputs.  The outputs keep the envelope's dense shapes: x +0.0 and base
+// -1 behind the problem's own lengths, the objective row in envelope columns (structural entries at
+// 1 + j, slack entries at 1 + n + i, artificial entries at 1 + n + m + i), +0.0 everywhere else.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE) void k_batch_solve_rag(BatchRagArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    __shared__ double s_v[16];
+    __shared__ int s_i[16];
+    __shared__ double s_rv;
+    __shared__ int s_ri;
+    __shared__ unsigned s_k;
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m, N1 = 1 + n + 2 * m;
+    // wg_by_col's rule, decided once: the strides are the launch's
+    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    for (;;) {
+        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const unsigned turn = s_k;
+        if (turn >= (unsigned)a.count) return;
+        // the problem and its dimensions are the same in every lane: kept in scalar registers
+        const int k = __builtin_amdgcn_readfirstlane(a.order != nullptr ? a.order[turn] : (int)turn);
+        if ((unsigned)k >= (unsigned)a.count) {  // not a problem of this call: skipped
+            __syncthreads();                     // (s_k is rewritten next)
+            continue;
+        }
+        const int nk = __builtin_amdgcn_readfirstlane(a.n_k[k]), mk = __builtin_amdgcn_readfirstlane(a.m_k[k]);
+        const bool good = nk >= 1 && mk >= 1 && nk <= n && mk <= m && sx_batch_lay(nk, mk).total <= a.set;
+        // a problem that fails the test is carried through the epilogue as 0 x 0: nothing is carved
+        // for it, nothing of it is read, and every output is cleared
+        const int en = good ? nk : 0, em = good ? mk : 0, Ns = 1 + en + em;
+        const BatchWork w = wg_carve(W, en, em);
+        TwoPhase t{SX_BAD_SHAPE, false, 0, 0};
+        if (good) {
+            const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(en, em);
+            const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
+                               a.c + (long long)k * a.c_sb, a.c_sj};
+            WG_TWO_PHASE(t, w, src, by_col, a.max_pivots, budget, s_v, s_i, &s_rv, &s_ri);
+        }
+        const bool feasible = t.status == SX_FEASIBLE, evicted = t.status == SX_EVICTED;
+        if (a.x != nullptr) {
+            // k_batch_solve_dev's staging in the pivot-row copy, over the problem's own entries
+            for (int j = threadIdx.x; j < en; j += SX_TILE) w.prow[j] = 0.0;
+            __syncthreads();
+            if (feasible)
+                for (int i = threadIdx.x; i < em; i += SX_TILE) {
+                    const unsigned bi = (unsigned)w.base[i];
+                    if (bi < (unsigned)en) w.prow[bi] = w.T[(size_t)i * w.ld];
+                }
+            __syncthreads();
+            double *x = a.x + (size_t)k * (size_t)n;
+            for (int j = threadIdx.x; j < n; j += SX_TILE) x[j] = j < en ? w.prow[j] : 0.0;
+        }
+        if (a.base != nullptr) {
+            int *base_out = a.base + (size_t)k * (size_t)m;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = i < em ? w.base[i] : -1;
+        }
+        // the problem's own logical width, as k_batch_solve_dev reports it
+        const int width = evicted || !good ? 0 : t.ph2 ? Ns : Ns + em;
+        if (a.objrow != nullptr) {
+            double *row = a.objrow + (size_t)k * (size_t)N1;
+            for (int j = threadIdx.x; j < N1; j += SX_TILE) {
+                // envelope column j -> the problem's logical column l, or -1 where it has none
+                int l;
+                if (j <= n)
+                    l = j <= en ? j : -1;
+                else if (j <= n + m)
+                    l = j - n - 1 < em ? 1 + en + (j - n - 1) : -1;
+                else
+                    l = j - n - m - 1 < em ? Ns + (j - n - m - 1) : -1;
+                row[j] = l >= 0 && l < width ? w.d[l] : 0.0;
+            }
+        }
+        if (threadIdx.x == 0) {
+            a.status[k] = evicted ? SX_NOT_ENDED : t.status;
+            a.pivots[2 * (size_t)k] = t.p1;
+            a.pivots[2 * (size_t)k + 1] = t.p2;
+            a.opt[k] = feasible ? w.d[0] : __builtin_nan("");
+            if (a.row_width != nullptr) a.row_width[k] = width;
+            if (evicted) atomicAdd(a.evicted, 1);
+        }
+        __syncthreads();  // the next problem overwrites the working set and s_k
+    }
+}
+
 // One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
 template <class Args, void (*KL)(Args), void (*KW)(Args)>
 struct Entry {
@@ -404,6 +495,7 @@ struct Entry {
 };
 using HostEntry = Entry<BatchArgs, k_batch_solve<true>, k_batch_solve<false>>;
 using DevEntry = Entry<BatchDevArgs, k_batch_solve_dev<true>, k_batch_solve_dev<false>>;
+using RagEntry = Entry<BatchRagArgs, k_batch_solve_rag<true>, k_batch_solve_rag<false>>;
 
 }  // namespace
 
@@ -415,4 +507,8 @@ void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_by
 }
 void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     DevEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+int sx_batch_resident_rag(bool lds, size_t lds_bytes) { return RagEntry::resident(lds, lds_bytes); }
+void sx_launch_batch_solve_rag(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    RagEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

@@ -17,6 +17,7 @@
 #define SX_NOT_ENDED (-10)
 #define SX_PIVOT_CAP (-11)     // opt-in pivot budget reached (off in parity mode)
 #define SX_NUMERIC_FAIL (-12)  // ratio argmin returned no row although a pivot is eligible
+#define SX_BAD_SHAPE (-14)     // ragged device batch: a problem's dimensions lie outside the envelope (-13: SX_HANG)
 
 #define SX_TILE 512     // argmin tile = reference THREADS (reduction.cu:6)
 #define SX_EPS 1e-9     // macro.h:28
@@ -429,11 +430,21 @@ struct BatchDevArgs {
     double *ws;            // workspace-resident: the slices; null for the LDS class
     long long slice;       // doubles per slice
 };
+// The ragged device entry (simplex_solve_batch_device_ragged): BatchDevArgs, whose n and m are now
+// the envelope every input and output array is shaped by, plus the per-problem dimensions.  Problem
+// k is the n_k[k] x m_k[k] leading block of its envelope slot; nothing outside that block is read.
+struct BatchRagArgs : BatchDevArgs {
+    const int *n_k, *m_k;  // [count] device; out of [1, n] / [1, m]: the problem gets SX_BAD_SHAPE
+    const int *order;      // [count] device or null (identity): the work counter's value -> problem
+    long long set;         // doubles of the envelope's working set, sx_batch_lay(n, m).total
+};
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
 // workgroups of the batch kernel (dev: of the device-resident entry's kernel) the current device
 // holds at once with this much dynamic LDS
 int sx_batch_resident(bool lds, size_t lds_bytes, bool dev = false);
+int sx_batch_resident_rag(bool lds, size_t lds_bytes);  // ... of the ragged device entry's kernel
 void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve_rag(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s);

@@ -25,6 +25,7 @@
 #include "../../include/twoPhaseMethod.h"
 #include "sx_common.hpp"
 static_assert(SX_MAXW == SIMPLEX_MAX_GPUS, "simplex_hip.h SIMPLEX_MAX_GPUS is the engine's shard limit");
+static_assert(SX_BAD_SHAPE == SIMPLEX_BAD_SHAPE, "simplex_hip.h SIMPLEX_BAD_SHAPE is the ragged batch kernel's status");
 
 // ------------------------------------------------------------------ errors (error.cu:5-18)
 void sx_handle_error(hipError_t err, const char *file, int line) {
@@ -2574,6 +2575,52 @@ int simplex_solve_batch_device(const simplex_batch_device_t *args) {
     SX_HIP(hipMemsetAsync(args->workspace, 0, SX_BATCH_DEV_HEADER, s));
     SX_HIP(hipMemsetAsync(args->evicted, 0, sizeof(int), s));
     sx_launch_batch_solve_dev(cls == 2, a, grid, (size_t)set * sizeof(double), s);
+    return 0;
+}
+
+// The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
+// The launch is the envelope's: its class, its working set (LDS bytes or slice), and a grid no
+// larger than simplex_batch_device_workspace(n, m, count) paid for.  The per-problem dimensions are
+// device data, so the kernel tests them (SX_BAD_SHAPE).  Every return code that needs no residency
+// figure is decided before the first runtime call; only class 1's workspace size needs one.
+int simplex_solve_batch_device_ragged(const simplex_batch_device_t *args, const int *n_k, const int *m_k,
+                                      const int *order) {
+    if (args == nullptr || args->count < 0) return -1;
+    const int n = args->n, m = args->m, count = args->count;
+    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
+    if (cls == 0) return -3;
+    if (count == 0) return 0;
+    if (n_k == nullptr || m_k == nullptr || args->status == nullptr || args->pivots == nullptr ||
+        args->opt == nullptr || args->evicted == nullptr)
+        return -2;
+    const SxSource src{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj};
+    const int rc = device_source_check(n, m, src, true, count, args->A_sb, args->b_sb, args->c_sb);
+    if (rc != 0) return rc;
+    if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0 ||
+        args->workspace_bytes < SX_BATCH_DEV_HEADER)
+        return -5;
+    const long long set = sx_batch_lay(n, m).total;
+    int grid = std::min(count, sx_batch_resident_rag(cls == 2, (size_t)set * sizeof(double)));
+    if (cls == 1) {
+        const int slices = batch_device_grid(n, m, count, cls);  // what the workspace query counted
+        if (args->workspace_bytes < SX_BATCH_DEV_HEADER + (long long)slices * set * (long long)sizeof(double)) return -5;
+        grid = std::min(grid, slices);
+    }
+
+    BatchRagArgs a{{n, m, count,
+                    args->A, args->A_sb, args->A_sr, args->A_sc, args->b, args->b_sb, args->b_si, args->c, args->c_sb,
+                    args->c_sj, args->max_pivots, g_batch_budget,
+                    args->status, args->pivots, args->opt, args->x, args->base, args->objrow, args->row_width,
+                    args->evicted, static_cast<unsigned *>(args->workspace)},
+                   n_k, m_k, order, set};
+    if (cls == 1) {
+        a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
+        a.slice = set;
+    }
+    hipStream_t s = static_cast<hipStream_t>(args->stream);
+    SX_HIP(hipMemsetAsync(args->workspace, 0, SX_BATCH_DEV_HEADER, s));
+    SX_HIP(hipMemsetAsync(args->evicted, 0, sizeof(int), s));
+    sx_launch_batch_solve_rag(cls == 2, a, grid, (size_t)set * sizeof(double), s);
     return 0;
 }
 
