@@ -194,6 +194,10 @@ void simplex_set_batch_budget(long long pivots);
  * launch) on the current device: it allocates nothing, copies nothing, never synchronises and keeps
  * no state, so calls on different streams with different outputs and workspaces are independent.
  * The inputs are not written; outputs and workspace must not overlap them or each other.
+ * Element strides may be negative: A, b and c are the addresses of the logical first elements (the
+ * last ones in memory along a reversed dimension) and A[k][i][j] is read at
+ * A + k * A_sb + i * A_sr + j * A_sc whatever the signs.  The same holds for the ragged entry,
+ * simplex_solve_device and simplex_dev_build_phase1_device; only a stride of 0 is refused (-4).
  * Per problem the results are twoPhaseMethodEx's: status, pivots (phase 1, phase 2) and base as
  * there; for a FEASIBLE problem opt and x bit for bit, for any other status opt is a quiet NaN and
  * x is all +0.0 (never stale memory).  objrow[k] is what simplex_last_objective_row reports for
@@ -263,7 +267,8 @@ int simplex_solve_batch_device_ragged(const simplex_batch_device_t *args, const 
 
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through
- * element strides (a transposed or sliced view is not copied), each shard builds its rows of the
+ * element strides (a transposed or sliced view is not copied; negative strides are accepted, with
+ * A, b and c the addresses of the logical first elements), each shard builds its rows of the
  * phase-1 tableau straight from them, and the results are left on the device.  No host copy and no
  * second device copy of A is made (copies of O(m + n) are); one 4-byte read-back decides slack
  * compaction by twoPhaseMethodEx's rule (no b[i] < 0.0).  Every shard setting is honoured as in

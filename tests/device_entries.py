@@ -1,0 +1,199 @@
+"""A C-level caller of the device entries (include/simplex_hip.h), for what sx.solve_batch_tensors and
+sx.solve_tensors never pass: explicit base pointers and element strides (negative ones included),
+optional outputs left NULL, a caller-made workspace.  ctypes over _lib.BatchDeviceT / _lib.DeviceSolveT:
+
+  workspace                    simplex_batch_device_workspace
+  batch_device                 simplex_solve_batch_device, simplex_solve_batch_device_ragged
+  solve_device                 simplex_solve_device
+  build_phase1_device          simplex_dev_build_phase1_device
+
+A source is a Src: a device address, element strides, and the tensor that owns the memory.  Every
+output the helper allocates is pre-filled with SENTINEL (-777.0, -777 for ints), so "not written" can
+be asserted.  guarded() places data in the middle third of one allocation whose outer thirds hold a
+fill value (NaN for inputs, SENTINEL for a workspace): a walk with the wrong sign or one slice too
+many stays inside the allocation and shows up as a failed comparison, never as a fault."""
+import ctypes
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from simplexoncuda_amd import _lib
+
+SENTINEL = -777.0
+ALLOC = object()  # an optional output: allocate it (pre-filled); None: pass NULL; a tensor: use it
+
+
+class Src:
+    """a strided source in device memory: element e of the logical array lies at ptr + 8 * sum(e * strides)"""
+
+    def __init__(self, ptr, strides, owner):
+        self.ptr, self.strides, self.owner = int(ptr), tuple(int(s) for s in strides), owner
+
+
+def dense(t):
+    """a Src of a torch tensor (its own strides, which are never negative)"""
+    return Src(t.data_ptr(), t.stride(), t)
+
+
+def guarded(data, fill=float("nan")):
+    """data (a float64 array) in the middle third of one device allocation of three times its size,
+    `fill` in the outer thirds: (the whole allocation, its middle third as a flat view)"""
+    flat = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+    L = len(flat)
+    whole = torch.full((3 * L,), fill, dtype=torch.float64, device="cuda")
+    whole[L:2 * L] = torch.from_numpy(flat).cuda()
+    return whole, whole[L:2 * L]
+
+
+def flipped(arr, axes=()):
+    """the logical array `arr` stored reversed along `axes` in a guarded buffer: a Src whose strides
+    along those axes are negative and whose base pointer is the logical element [0, ..., 0] -- the
+    last one of each reversed dimension in memory.  The instance must not be symmetric under the flip
+    (a sign error could pass otherwise); only a dimension of length 1 cannot tell"""
+    arr = np.asarray(arr, dtype=np.float64)
+    axes = tuple(axes)
+    stored = np.ascontiguousarray(np.flip(arr, axes)) if axes else np.ascontiguousarray(arr)
+    for ax in axes:
+        if arr.shape[ax] > 1:
+            rev, fwd = np.flip(arr, ax).view(np.uint64), arr.view(np.uint64)
+            assert not np.array_equal(rev, fwd), f"the array is symmetric along axis {ax}"
+    whole, mid = guarded(stored)
+    dense_strides = [int(np.prod(arr.shape[k + 1:], dtype=np.int64)) for k in range(arr.ndim)]
+    offset = sum((arr.shape[ax] - 1) * dense_strides[ax] for ax in axes)
+    strides = [-d if k in axes else d for k, d in enumerate(dense_strides)]
+    assert 0 <= offset < max(stored.size, 1)
+    return Src(mid.data_ptr() + 8 * offset, strides, whole)
+
+
+def unchanged(src, data, axes=()):
+    """the guarded buffer of flipped(data, axes) still holds exactly what was put there"""
+    flat = np.ascontiguousarray(np.flip(np.asarray(data, dtype=np.float64), tuple(axes))).reshape(-1)
+    L = len(flat)
+    want = np.full(3 * L, float("nan"))
+    want[L:2 * L] = flat
+    return np.array_equal(src.owner.cpu().numpy().view(np.uint64), want.view(np.uint64))
+
+
+def guarded_workspace(nbytes, guard_bytes):
+    """a workspace of exactly nbytes in front of a guard band of guard_bytes, all of it SENTINEL
+    doubles: (the allocation as uint8, the guard band as an int64 view)"""
+    assert nbytes % 8 == 0 and guard_bytes % 8 == 0
+    whole = torch.full(((nbytes + guard_bytes) // 8,), SENTINEL, dtype=torch.float64, device="cuda")
+    return whole.view(torch.uint8), whole[nbytes // 8:].view(torch.int64)
+
+
+def sentinel_bits():
+    return int(np.array([SENTINEL]).view(np.int64)[0])
+
+
+def workspace(n, m, count):
+    return int(_lib.load().simplex_batch_device_workspace(n, m, count))
+
+
+def slices(n, m, count=2 ** 30):
+    """working-set slices the workspace query counts for a class-1 shape, and the doubles of one"""
+    one = workspace(n, m, 1) - 256
+    assert one > 0 and one % 8 == 0 and (workspace(n, m, count) - 256) % one == 0
+    return (workspace(n, m, count) - 256) // one, one // 8
+
+
+def _out(arg, shape, dtype):
+    if arg is None:
+        return None
+    if arg is ALLOC:
+        return torch.full(shape, SENTINEL if dtype == torch.float64 else int(SENTINEL), dtype=dtype, device="cuda")
+    assert tuple(arg.shape) == tuple(shape) and arg.dtype == dtype and arg.is_contiguous()
+    return arg
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def batch_device(A, b, c, n, m, count, x=ALLOC, base=ALLOC, objrow=ALLOC, row_width=ALLOC, max_pivots=-1, ws=None,
+                 ws_bytes=None, n_k=None, m_k=None, order=None, ragged=False):
+    """simplex_solve_batch_device, or with ragged=True (or n_k / m_k / order) the ragged entry; A, b, c
+    are Srcs with strides (batch, row, column), (batch, i), (batch, j); ws: a uint8 tensor whose
+    first ws_bytes (default: all of it) are the workspace, None: exactly the query's bytes.  Waits for
+    the launch.  Returns the output tensors (None where NULL was passed), evicted and rc"""
+    lib = _lib.load()
+    ragged = ragged or n_k is not None or m_k is not None or order is not None
+    N1 = 1 + n + 2 * m
+    o = SimpleNamespace(
+        status=_out(ALLOC, (count,), torch.int32), pivots=_out(ALLOC, (count, 2), torch.int64),
+        opt=_out(ALLOC, (count,), torch.float64), x=_out(x, (count, n), torch.float64),
+        base=_out(base, (count, m), torch.int32), objrow=_out(objrow, (count, N1), torch.float64),
+        row_width=_out(row_width, (count,), torch.int32), evicted=_out(ALLOC, (1,), torch.int32))
+    if ws is None:
+        ws = torch.empty(workspace(n, m, count), dtype=torch.uint8, device="cuda")
+    if ws_bytes is None:
+        ws_bytes = ws.numel()
+    assert ws.dtype == torch.uint8 and 0 <= ws_bytes <= ws.numel()
+    args = _lib.BatchDeviceT(
+        n=n, m=m, count=count,
+        A=A.ptr, A_sb=A.strides[0], A_sr=A.strides[1], A_sc=A.strides[2],
+        b=b.ptr, b_sb=b.strides[0], b_si=b.strides[1],
+        c=c.ptr, c_sb=c.strides[0], c_sj=c.strides[1],
+        max_pivots=max_pivots,
+        status=o.status.data_ptr(), pivots=o.pivots.data_ptr(), opt=o.opt.data_ptr(), x=_ptr(o.x), base=_ptr(o.base),
+        objrow=_ptr(o.objrow), row_width=_ptr(o.row_width), evicted=o.evicted.data_ptr(),
+        workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
+        stream=torch.cuda.current_stream().cuda_stream)
+    if ragged:
+        full = lambda v: torch.full((count,), v, dtype=torch.int32, device="cuda")  # noqa: E731
+        n_k = full(n) if n_k is None else n_k
+        m_k = full(m) if m_k is None else m_k
+        assert all(t.dtype == torch.int32 and tuple(t.shape) == (count,) and t.is_contiguous()
+                   for t in (n_k, m_k) + (() if order is None else (order,)))
+        o.rc = lib.simplex_solve_batch_device_ragged(ctypes.byref(args), n_k.data_ptr(), m_k.data_ptr(), _ptr(order))
+    else:
+        o.rc = lib.simplex_solve_batch_device(ctypes.byref(args))
+    torch.cuda.current_stream().synchronize()
+    o.ws = ws
+    return o
+
+
+def as_batch_tensors(o, n_k=None, m_k=None, keep=None):
+    """batch_device's outputs as the sx.BatchTensors that batch_refs.same_as_refs and
+    test_gpu_batch_ragged.same_as_ragged_refs compare (keep: the problems to keep, a list of indices)"""
+    import simplexoncuda_amd as sx
+
+    pick = (lambda t: t) if keep is None else (lambda t: None if t is None else t[keep])
+    return sx.BatchTensors(pick(o.status), pick(o.pivots), pick(o.opt), pick(o.x), pick(o.base), pick(o.objrow),
+                           pick(o.row_width), int(o.evicted.item()), pick(n_k), pick(m_k))
+
+
+def solve_device(A, b, c, n, m, x=ALLOC, base=ALLOC, objrow=ALLOC, opt=True, row_width=True, max_pivots=-1):
+    """simplex_solve_device; A, b, c are Srcs with strides (row, column), (i,), (j,); opt / row_width
+    False: NULL is passed for opt_out / row_width_out.  Returns status, pivots, opt and row_width
+    (None where NULL was passed), the output tensors and rc"""
+    lib = _lib.load()
+    o = SimpleNamespace(x=_out(x, (n,), torch.float64), base=_out(base, (m,), torch.int32),
+                        objrow=_out(objrow, (1 + n + 2 * m,), torch.float64))
+    args = _lib.DeviceSolveT(
+        n=n, m=m, A=A.ptr, A_sr=A.strides[0], A_sc=A.strides[1], b=b.ptr, b_si=b.strides[0], c=c.ptr, c_sj=c.strides[0],
+        max_pivots=max_pivots, x=_ptr(o.x), base=_ptr(o.base), objrow=_ptr(o.objrow),
+        stream=torch.cuda.current_stream().cuda_stream)
+    status, optv, width = ctypes.c_int(int(SENTINEL)), ctypes.c_double(SENTINEL), ctypes.c_int(int(SENTINEL))
+    piv = (ctypes.c_longlong * 2)(int(SENTINEL), int(SENTINEL))
+    o.rc = lib.simplex_solve_device(ctypes.byref(args), ctypes.byref(status), ctypes.byref(optv) if opt else None, piv,
+                                    ctypes.byref(width) if row_width else None)
+    assert opt or optv.value == SENTINEL
+    assert row_width or width.value == int(SENTINEL)
+    o.status, o.pivots = status.value, (piv[0], piv[1])
+    o.opt, o.row_width = (optv.value if opt else None), (width.value if row_width else None)
+    return o
+
+
+def build_phase1_device(A, b, n, m):
+    """simplex_dev_build_phase1_device; A, b are Srcs with strides (row, column), (i,): (T, d, base) on the host"""
+    lib = _lib.load()
+    N1 = 1 + n + 2 * m
+    T, d, base = np.zeros((m, N1)), np.zeros(N1), np.zeros(m, dtype=np.int32)
+    torch.cuda.synchronize()  # (the hook takes no stream)
+    rc = lib.simplex_dev_build_phase1_device(n, m, A.ptr, A.strides[0], A.strides[1], b.ptr, b.strides[0],
+                                             T.ctypes.data_as(_lib.c_double_p), N1, d.ctypes.data_as(_lib.c_double_p),
+                                             base.ctypes.data_as(_lib.c_int_p))
+    assert rc == 0, rc
+    return T, d, base
