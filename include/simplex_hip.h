@@ -20,6 +20,7 @@ extern "C" {
 #define SIMPLEX_NUMERIC_FAIL -12 /* eligible pivot but the ratio argmin found no row */
 #define SIMPLEX_HANG -13         /* fused batch: an in-kernel hand-off timed out (never expected) */
 #define SIMPLEX_BAD_SHAPE -14    /* ragged device batch: a problem's dimensions lie outside the envelope */
+#define SIMPLEX_BAD_STATE -15    /* state entry: a problem's saved state fails the kernel's checks */
 #define SIMPLEX_MAX_GPUS 8       /* shards (GPUs) one solve can use: simplex_set_gpus, SIMPLEX_GPUS, --gpus */
 
 /* ---- configuration ---- */
@@ -205,7 +206,8 @@ void simplex_set_batch_budget(long long pivots);
  * and +0.0 from row_width[k] up to 1+n+2m.
  * A problem that exhausts the resident pivot budget (simplex_set_batch_budget) is NOT re-solved
  * here: it is left with status SIMPLEX_NOT_ENDED, opt NaN, x zero and row_width 0, and counted in
- * *evicted; the caller re-solves it with twoPhaseMethodEx (no other path gives NOT_ENDED).
+ * *evicted; the caller re-solves it with twoPhaseMethodEx (no other path gives NOT_ENDED), or
+ * keeps its state and continues it on the device with simplex_solve_batch_device_state (below).
  * Shard settings are ignored, as in simplex_solve_batch. */
 typedef struct {
     int n, m, count;                       /* every problem n variables x m constraints */
@@ -264,6 +266,51 @@ int simplex_solve_batch_device(const simplex_batch_device_t *args);
  * enqueues two small memsets and one launch on `stream`. */
 int simplex_solve_batch_device_ragged(const simplex_batch_device_t *args, const int *n_k, const int *m_k,
                                       const int *order /* or NULL */);
+
+/* ---- device batch state: resume capped or evicted problems, warm-start new costs ---- */
+/* simplex_solve_batch_device that can keep each problem's final working set on the device and start
+ * from a kept one.  A state is dense per problem and belongs to one shape (n, m) and count:
+ * T holds the 1+n+m stored columns b | structural | slack (in phase 1 the artificial block is the
+ * slack block bit for bit, so it is not kept), d the objective row at the full width 1+n+2m
+ * (entries [1+n+m, 1+n+2m) are +0.0 in a phase-2 state), base the basis, phase where the problem
+ * stands (1: in phase 1, 2: in phase 2, 0: no state) and pivots the pivots done so far per phase.
+ *
+ * in == NULL: a fresh solve -- exactly simplex_solve_batch_device, every output bit for bit -- whose
+ * final working sets are written to out.
+ * in != NULL: a resume.  args->A and args->b are not read and may be NULL; args->c is required (it is
+ * read when a phase-1 state reaches phase 2, and for recost) and only its strides are checked.  Each
+ * problem's T, d and base are loaded instead of being built, and the two-phase loop is re-entered:
+ * a phase-1 state continues phase 1 at pivots[0], and when that ends FEASIBLE runs phase 2 from 0
+ * with args->c; a phase-2 state continues phase 2 at pivots[1], or with recost != 0 (the warm start
+ * for new costs on the same constraints) restarts phase 2 from pivot 0 on the saved tableau and
+ * basis with d[0] = +0.0, d[1+j] = -c[j], the slack entries +0.0, made canonical for the basis;
+ * pivots[0] is kept.  No outcome has a case of its own: a state that ended FEASIBLE, UNBOUNDED,
+ * INFEASIBLE, DEGENERATE or NUMERIC_FAIL gives that status again with no new pivot.
+ * max_pivots caps each phase's total, saved plus new, as one call would: a capped call followed by a
+ * resume with -1 is the uncapped solve, bit for bit, in every output and in the state.  The resident
+ * budget (simplex_set_batch_budget) counts the pivots of THIS call per phase, so a problem left
+ * SIMPLEX_NOT_ENDED progresses with every resume; it is left with the state a cap at the same count
+ * leaves, and resumed here instead of re-solved by twoPhaseMethodEx.
+ * out == NULL: the state is not kept.  out may equal in, member for member (a workgroup owns its
+ * problem and has loaded all of it before it writes); any other overlap is the caller's error.
+ * The host cannot see a state, so the kernel tests it before it indexes anything with it: phase must
+ * be 1 or 2, both pivot counts >= 0, every base[i] in [0, n+2m) in phase 1 and [0, n+m) in phase 2.
+ * A problem that fails gets the status SIMPLEX_BAD_STATE, pivots 0, opt NaN, x zero, base -1, a zero
+ * row, row_width 0 and out->phase 0 (nothing else of out is written for it); the other problems of
+ * the call are not affected.
+ * Returns simplex_solve_batch_device's codes; -2 also for a NULL member of a non-NULL state struct
+ * and for a NULL c with in != NULL.  The workspace is simplex_batch_device_workspace(n, m, count).
+ * Like that entry the call only enqueues two small memsets and one launch on `stream`. */
+typedef struct {
+    double *T;          /* [count][m][1+n+m]  stored columns b | structural | slack, row-major, dense */
+    double *d;          /* [count][1+n+2m]    objective row */
+    int *base;          /* [count][m] */
+    int *phase;         /* [count]            1: in phase 1, 2: in phase 2, 0: no state */
+    long long *pivots;  /* [count][2]         pivots done so far in phase 1, phase 2 */
+} simplex_batch_state_t;
+int simplex_solve_batch_device_state(const simplex_batch_device_t *args,
+                                     const simplex_batch_state_t *in /* NULL: fresh solve */,
+                                     const simplex_batch_state_t *out /* NULL: state not kept */, int recost);
 
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through

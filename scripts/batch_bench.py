@@ -9,11 +9,12 @@ tensors, are also solved with solve_batch_tensors (default arguments, and object
 same host clock, each call followed by torch.cuda.synchronize(), the three batched paths taking
 turns inside every repeat.  The ragged leg (ragged_leg below) then times the ragged device entry
 against the one-shape entry on the same uniform instances, and against solve_batch on problems whose
-dimensions vary inside a 64 x 64 envelope.  The rates are printed and written to
+dimensions vary inside a 64 x 64 envelope; the state leg (state_leg) what keeping the batch state
+costs and what a warm start from it saves.  The rates are printed and written to
 profiles/batch_bench.txt (or --out).
 
-    python scripts/batch_bench.py [--problems 1024] [--subset 64] [--repeats 7] [--legs all|uniform|ragged]
-                                  [--out FILE]
+    python scripts/batch_bench.py [--problems 1024] [--subset 64] [--repeats 7]
+                                  [--legs all|uniform|ragged|state] [--out FILE]
 """
 import argparse
 import os
@@ -124,6 +125,52 @@ def ragged_leg(args):
     return lines
 
 
+def state_leg(args):
+    """The batch state (solve_batch_tensors(keep_state=True), resume_batch_tensors), two questions on
+    the SHAPES' instances, the four calls taking turns inside every repeat: what keeping the state
+    costs (the same solve with and without it), and what the warm start saves -- new costs
+    c (1 + 0.1 u), u uniform in [-1, 1], solved by re-costing the kept optimum (recost=True, into a
+    new state, so every repeat starts from the same one) and from scratch, after asserting that both
+    end in the same status on every instance."""
+    ms = lambda t: f"{statistics.median(t) * 1e3:.3f}"  # noqa: E731
+    med = statistics.median
+    lines = ["# state: n m problems solve_ms solve_min_ms solve_max_ms keep_state_ms keep_over_solve recost_ms "
+             "scratch_new_costs_ms scratch_over_recost warm_pivots_mean scratch_pivots_mean"]
+    for n, m in SHAPES:
+        probs = [sx.generateRandomProblem(n, m, 7919 * k + n * 100 + m, 1, 100) for k in range(args.problems)]
+        A, b, c = device_tensors(probs)
+        for p in probs:
+            p.close()
+        u = torch.from_numpy(np.random.default_rng(n * 100 + m).uniform(-1.0, 1.0, size=tuple(c.shape))).cuda()
+        c2 = c * (1.0 + 0.1 * u)
+        kept = sx.solve_batch_tensors(A, b, c, keep_state=True)
+        warm = sx.resume_batch_tensors(kept.state, c2, recost=True, in_place=False)
+        scratch = sx.solve_batch_tensors(A, b, c2)
+        assert kept.evicted == 0 and warm.evicted == 0 and scratch.evicted == 0
+        assert torch.equal(warm.status, scratch.status)
+        piv_warm = float(warm.pivots[:, 1].double().mean())
+        piv_scratch = float(scratch.pivots.sum(dim=1).double().mean())
+
+        def timed(fn):
+            def run():
+                fn()
+                torch.cuda.synchronize()
+            return run
+
+        fns = [timed(lambda: sx.solve_batch_tensors(A, b, c)),
+               timed(lambda: sx.solve_batch_tensors(A, b, c, keep_state=True)),
+               timed(lambda: sx.resume_batch_tensors(kept.state, c2, recost=True, in_place=False)),
+               timed(lambda: sx.solve_batch_tensors(A, b, c2))]
+        seconds_in_turn(fns, 2)  # warm-up
+        t_one, t_keep, t_warm, t_new = seconds_in_turn(fns, args.repeats)
+        line = (f"{n} {m} {len(probs)} {ms(t_one)} {min(t_one) * 1e3:.3f} {max(t_one) * 1e3:.3f} {ms(t_keep)} "
+                f"{med(t_keep) / med(t_one):.3f} {ms(t_warm)} {ms(t_new)} {med(t_new) / med(t_warm):.2f} "
+                f"{piv_warm:.1f} {piv_scratch:.1f}")
+        print(line, flush=True)
+        lines.append(line)
+    return lines
+
+
 def mixed_dims_case(args, dims, n, m):
     """problems of the given (n_k, m_k) in an n x m envelope whose padding is NaN: solve_batch on the
     host problems and the ragged entry in turn; then the ragged entry with its default order (built
@@ -169,16 +216,16 @@ def main():
     ap.add_argument("--problems", type=int, default=1024)
     ap.add_argument("--subset", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--legs", choices=["all", "uniform", "ragged"], default="all")
+    ap.add_argument("--legs", choices=["all", "uniform", "ragged", "state"], default="all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.txt"))
     args = ap.parse_args()
 
     lines = [f"# scripts/batch_bench.py --problems {args.problems} --subset {args.subset} --repeats {args.repeats}"
              + ("" if args.legs == "all" else f" --legs {args.legs}")]
-    if args.legs != "ragged":
+    if args.legs in ("all", "uniform"):
         lines.append("# n m problems class batch_LPs_per_s loop_LPs_per_s ratio batch_ms loop_ms_per_LP "
                      "tensors_ms tensors_row_ms batch_ms_over_tensors_ms")
-    for n, m in SHAPES if args.legs != "ragged" else []:
+    for n, m in SHAPES if args.legs in ("all", "uniform") else []:
         probs = [sx.generateRandomProblem(n, m, 7919 * k + n * 100 + m, 1, 100) for k in range(args.problems)]
         subset = probs[:args.subset]
         # the two paths agree on the subset (and this warms both up)
@@ -211,8 +258,10 @@ def main():
         lines.append(line)
         for p in probs:
             p.close()
-    if args.legs != "uniform":
+    if args.legs in ("all", "ragged"):
         lines += ragged_leg(args)
+    if args.legs in ("all", "state"):
+        lines += state_leg(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -74,6 +74,14 @@ class BatchDeviceT(ctypes.Structure):
     ]
 
 
+class BatchStateT(ctypes.Structure):
+    """simplex_batch_state_t (include/simplex_hip.h); every pointer is a device address."""
+    _fields_ = [
+        ("T", ctypes.c_void_p), ("d", ctypes.c_void_p), ("base", ctypes.c_void_p), ("phase", ctypes.c_void_p),
+        ("pivots", ctypes.c_void_p),
+    ]
+
+
 class DeviceSolveT(ctypes.Structure):
     """simplex_device_solve_t (include/simplex_hip.h); every pointer is a device address."""
     _fields_ = [
@@ -157,6 +165,8 @@ SIGNATURES = {
     "simplex_solve_batch_device": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT)]),
     "simplex_solve_batch_device_ragged": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.c_void_p, ctypes.c_void_p,
                                                          ctypes.c_void_p]),
+    "simplex_solve_batch_device_state": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.POINTER(BatchStateT),
+                                                        ctypes.POINTER(BatchStateT), ctypes.c_int]),
     "simplex_solve_device": (ctypes.c_int, [ctypes.POINTER(DeviceSolveT), c_int_p, c_double_p, c_ll_p, c_int_p]),
     "simplex_problem_from_arrays": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "simplex_generate_problem_ex": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,

@@ -21,10 +21,20 @@ PIVOT_CAP = -11
 NUMERIC_FAIL = -12
 HANG = -13
 BAD_SHAPE = -14
+BAD_STATE = -15
 
 STATUS_NAMES = {FEASIBLE: "FEASIBLE", INFEASIBLE: "INFEASIBLE", UNBOUNDED: "UNBOUNDED",
                 DEGENERATE: "DEGENERATE", NOT_ENDED: "NOT_ENDED", PIVOT_CAP: "PIVOT_CAP",
                 NUMERIC_FAIL: "NUMERIC_FAIL", HANG: "HANG", BAD_SHAPE: "BAD_SHAPE"}
+# STATUS_NAMES holds the codes a solve from a problem can end with.  BAD_STATE belongs to a resume from
+# a saved state alone (resume_batch_tensors); status_name() names every code.
+STATE_STATUS_NAMES = {BAD_STATE: "BAD_STATE"}
+
+
+def status_name(status):
+    """the name of any status code, the state entry's BAD_STATE included; str(status) for an unknown one"""
+    status = int(status)
+    return STATUS_NAMES.get(status) or STATE_STATUS_NAMES.get(status, str(status))
 
 RAND_MSVC = 0
 RAND_GLIBC = 1
@@ -207,6 +217,36 @@ def solve_batch(problems, max_pivots=-1):
 
 
 @dataclass
+class BatchState:
+    """The saved working sets of a batch (simplex_batch_state_t): device tensors, one row per problem,
+    all contiguous.  Written by solve_batch_tensors(keep_state=True) and resume_batch_tensors, and
+    what resume_batch_tensors continues from."""
+    T: object        # float64 [B, m, 1 + n + m]: the stored columns b | structural | slack
+    d: object        # float64 [B, 1 + n + 2m]: the objective row
+    base: object     # int32 [B, m]
+    phase: object    # int32 [B]: 1 in phase 1, 2 in phase 2, 0 no state
+    pivots: object   # int64 [B, 2]: pivots done so far in phase 1, phase 2
+    n: int
+    m: int
+
+    @classmethod
+    def empty(cls, B, n, m, device):
+        """uninitialised tensors for a call to write (it writes every problem's phase; no fill is
+        launched here)"""
+        import torch
+
+        return cls(torch.empty((B, m, 1 + n + m), dtype=torch.float64, device=device),
+                   torch.empty((B, 1 + n + 2 * m), dtype=torch.float64, device=device),
+                   torch.empty((B, m), dtype=torch.int32, device=device),
+                   torch.empty(B, dtype=torch.int32, device=device),
+                   torch.empty((B, 2), dtype=torch.int64, device=device), n, m)
+
+    def _struct(self):
+        return _lib.BatchStateT(T=self.T.data_ptr(), d=self.d.data_ptr(), base=self.base.data_ptr(),
+                                phase=self.phase.data_ptr(), pivots=self.pivots.data_ptr())
+
+
+@dataclass
 class BatchTensors:
     """solve_batch_tensors' results: device tensors, one row per problem.  For a problem that is not
     FEASIBLE optimal_value is NaN and its solution row is zero; objective_row (when asked for) holds
@@ -229,6 +269,7 @@ class BatchTensors:
     evicted: object        # int; the device tensor (int32 [1]) with finish=False
     n_active: object = None  # int32 [B] after a ragged call
     m_active: object = None  # int32 [B] after a ragged call
+    state: object = None     # BatchState after keep_state=True or resume_batch_tensors
 
     @property
     def reduced_costs(self):
@@ -267,7 +308,7 @@ def _default_ragged_order(n_active, m_active):
 
 
 def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True, n_active=None, m_active=None,
-                        order=None):
+                        order=None, keep_state=False):
     """twoPhaseMethodEx of B problems of one shape held in device tensors (simplex_solve_batch_device):
     A [B, m, n], b [B, m], c [B, n], float64 on one ROCm device, read in place through their strides
     (a transposed or sliced view is not copied).  One launch on torch's current stream of that device
@@ -287,7 +328,12 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     for its own shape, in the conventions BatchTensors describes; dimensions outside the envelope
     give that problem BAD_SHAPE.  order: an int32 [B] permutation on A's device in which the
     workgroups take the problems; None builds larger-first on the device (no sync), False is 0..B-1.
-    Results do not depend on it."""
+    Results do not depend on it.
+
+    keep_state=True (simplex_solve_batch_device_state; not with the ragged arguments): the same
+    results, and every problem's final working set is kept in BatchTensors.state, a BatchState.
+    Problems left NOT_ENDED or PIVOT_CAP are then continued on the device by resume_batch_tensors:
+    none is re-solved on the host, and finish=True only reads the evicted count."""
     import torch
 
     B, m, n = _check_device_shapes("solve_batch_tensors", A, b, c, batch=True)
@@ -305,6 +351,8 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
             _check_ragged_arg("order", order, B, A.device)
     elif order is not None and order is not False:
         raise ValueError("solve_batch_tensors: order belongs to a ragged call (n_active, m_active)")
+    if keep_state and ragged:
+        raise ValueError("solve_batch_tensors: keep_state is not combined with a ragged call (n_active, m_active)")
     _check_device_placement("solve_batch_tensors", A, b, c)
     lib = _lib.load()
     dev = A.device
@@ -325,6 +373,7 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
                 order = _default_ragged_order(n_active, m_active)
             elif order is not False:
                 order = order.contiguous()
+        state = BatchState.empty(B, n, m, dev) if keep_state else None
         if B > 0:
             ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
             if ws_bytes < 0:
@@ -346,17 +395,100 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
                                                            None if order is False else order.data_ptr())
                 if rc < 0:
                     raise ValueError(f"simplex_solve_batch_device_ragged: bad arguments ({rc})")
+            elif keep_state:
+                rc = lib.simplex_solve_batch_device_state(ctypes.byref(args), None, ctypes.byref(state._struct()), 0)
+                if rc < 0:
+                    raise ValueError(f"simplex_solve_batch_device_state: bad arguments ({rc})")
             else:
                 rc = lib.simplex_solve_batch_device(ctypes.byref(args))
                 if rc < 0:
                     raise ValueError(f"simplex_solve_batch_device: bad arguments ({rc})")
         out = BatchTensors(status, pivots, opt, x, base, row, width, evicted,
-                           n_active if ragged else None, m_active if ragged else None)
+                           n_active if ragged else None, m_active if ragged else None, state)
         if not finish:
             return out
         out.evicted = int(evicted.item()) if B > 0 else 0
-        if out.evicted:
+        if out.evicted and not keep_state:
             _finish_evicted(out, A, b, c, max_pivots)
+    return out
+
+
+def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=False, finish=True, in_place=True):
+    """Continue the problems of a BatchState on the device (simplex_solve_batch_device_state): no A,
+    no b, no host copy.  c is [B, n] float64 on the state's device, any strides; it is read when a
+    phase-1 state reaches phase 2 and for recost.
+
+    A problem in phase 1 continues phase 1 behind its saved pivots and then runs phase 2 with c; one
+    in phase 2 continues phase 2, or with recost=True restarts phase 2 from pivot 0 on c from its
+    saved tableau and basis -- the warm start for new costs on the same constraints (phase 1 is not
+    repeated and its pivot count is kept).  max_pivots caps each phase's total, saved plus new, so a
+    capped solve resumed with -1 is the uncapped solve bit for bit; the resident budget
+    (set_batch_budget) counts this call's pivots, so a problem left NOT_ENDED progresses with every
+    resume.  A finished problem gives its status again without a pivot.  A state that fails the
+    kernel's checks gives that problem BAD_STATE, cleared outputs and phase 0.  BAD_STATE is not a
+    key of STATUS_NAMES: name a resume's statuses with status_name(code), not STATUS_NAMES[code].
+
+    in_place=True writes the new state over the old one (BatchTensors.state is `state`);
+    in_place=False allocates a new one and leaves `state` untouched.  finish=True reads the evicted
+    count (one 4-byte copy, which waits for the stream); finish=False returns right after the enqueue."""
+    import torch
+
+    if not isinstance(state, BatchState):
+        raise TypeError(f"resume_batch_tensors: state must be a BatchState, not {type(state).__name__}")
+    n, m = state.n, state.m
+    B = state.phase.shape[0]
+    dev = state.T.device
+    want = (("T", (B, m, 1 + n + m), torch.float64), ("d", (B, 1 + n + 2 * m), torch.float64),
+            ("base", (B, m), torch.int32), ("phase", (B,), torch.int32), ("pivots", (B, 2), torch.int64))
+    for name, shape, dtype in want:
+        t = getattr(state, name)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"resume_batch_tensors: state.{name} must be a contiguous {dtype} tensor of shape {shape}")
+        if t.device != dev:
+            raise ValueError("resume_batch_tensors: the state's tensors must be on one device")
+    if not isinstance(c, torch.Tensor):
+        raise TypeError(f"resume_batch_tensors: c must be a torch.Tensor, not {type(c).__name__}")
+    if c.dtype != torch.float64:
+        raise TypeError(f"resume_batch_tensors: c must be float64, not {c.dtype}")
+    if tuple(c.shape) != (B, n):
+        raise ValueError(f"resume_batch_tensors: c must be [{B}, {n}]; got {tuple(c.shape)}")
+    if n < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+        raise ValueError(f"resume_batch_tensors: no resident state exists for {n} variables x {m} constraints")
+    if dev.type != "cuda":
+        raise ValueError(f"resume_batch_tensors: the state is on {dev}; it must be on a GPU")
+    if c.device != dev:
+        raise ValueError(f"resume_batch_tensors: c is on {c.device}; it must be on the state's device, {dev}")
+    lib = _lib.load()
+    N1 = 1 + n + 2 * m
+    with torch.cuda.device(dev):
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        pivots = torch.empty((B, 2), dtype=torch.int64, device=dev)
+        opt = torch.empty(B, dtype=torch.float64, device=dev)
+        x = torch.empty((B, n), dtype=torch.float64, device=dev)
+        base = torch.empty((B, m), dtype=torch.int32, device=dev)
+        row = torch.empty((B, N1), dtype=torch.float64, device=dev) if objective_row else None
+        width = torch.empty(B, dtype=torch.int32, device=dev) if objective_row else None
+        evicted = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int32, device=dev)  # (the call zeroes it)
+        new = state if in_place else BatchState.empty(B, n, m, dev)
+        if B > 0:
+            ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
+            if ws_bytes < 0:
+                raise ValueError(f"simplex_batch_device_workspace: bad arguments ({ws_bytes})")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            args = _lib.BatchDeviceT(
+                n=n, m=m, count=B, c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1), max_pivots=max_pivots,
+                status=status.data_ptr(), pivots=pivots.data_ptr(), opt=opt.data_ptr(), x=x.data_ptr(),
+                base=base.data_ptr(), objrow=row.data_ptr() if objective_row else None,
+                row_width=width.data_ptr() if objective_row else None, evicted=evicted.data_ptr(),
+                workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
+                stream=torch.cuda.current_stream(dev).cuda_stream)
+            rc = lib.simplex_solve_batch_device_state(ctypes.byref(args), ctypes.byref(state._struct()),
+                                                      ctypes.byref(new._struct()), 1 if recost else 0)
+            if rc < 0:
+                raise ValueError(f"simplex_solve_batch_device_state: bad arguments ({rc})")
+        out = BatchTensors(status, pivots, opt, x, base, row, width, evicted, None, None, new)
+        if finish:
+            out.evicted = int(evicted.item()) if B > 0 else 0
     return out
 
 

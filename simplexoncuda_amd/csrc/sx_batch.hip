@@ -18,9 +18,10 @@
 // SxSource).  Its entries differ only in where a problem comes from and where its results go:
 // k_batch_solve (simplex_solve_batch: ragged problems packed by the host -- column-major A, the
 // source with A_sr = 1, A_sc = m -- results finished on the host), k_batch_solve_dev
-// (simplex_solve_batch_device: one shape, the caller's strides, every result written by the kernel)
-// and k_batch_solve_rag (simplex_solve_batch_device_ragged: the same with per-problem dimensions
-// inside one envelope shape).
+// (simplex_solve_batch_device: one shape, the caller's strides, every result written by the kernel),
+// k_batch_solve_rag (simplex_solve_batch_device_ragged: the same with per-problem dimensions
+// inside one envelope shape) and k_batch_solve_st (simplex_solve_batch_device_state: k_batch_solve_dev
+// that can load a problem's working set from a saved state and write it to one).
 
 #include <float.h>
 
@@ -102,17 +103,21 @@ __device__ __forceinline__ void wg_update_objective(const BatchWork &w, int N) {
     __syncthreads();
 }
 
-// orc_solve at width N: pivots until the phase ends, the cap is reached (SX_PIVOT_CAP) or one more
-// pivot would exceed the resident budget (SX_EVICTED).  Uniform over the workgroup.
+// orc_solve at width N, continued behind k0 pivots of the phase: pivots until the phase ends, the cap
+// on the phase's total is reached (SX_PIVOT_CAP) or one more pivot would exceed the resident budget
+// of this call, `budget` pivots behind k0 (SX_EVICTED).  That test sits behind the stop and unbounded
+// tests and in front of the first write to T, d or base, so an eviction leaves what a cap at the
+// same count leaves.  A fresh solve passes the literal 0 for k0.  Uniform over the workgroup.
 __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max_pivots, long long budget,
-                                        long long &pivots, double *s_v, int *s_i, double *s_rv, int *s_ri) {
+                                        long long k0, long long &pivots, double *s_v, int *s_i, double *s_rv,
+                                        int *s_ri) {
     const int n = w.n, m = w.m, ld = w.ld, Ns = 1 + n + m, art0 = Ns;
     // the row update gives each row to 16, 32 or 64 consecutive lanes (a row sweep by consecutive
     // lanes is conflict-free at any stride; narrow tableaux keep more rows in flight)
     const int g = Ns <= 16 ? 4 : Ns <= 32 ? 5 : 6;
     const int G = 1 << g, RP = SX_TILE >> g;
     const int rl = (int)threadIdx.x >> g, cl = (int)threadIdx.x & (G - 1);
-    long long k = 0;
+    long long k = k0;
     for (;;) {
         if (max_pivots >= 0 && k >= max_pivots) {
             pivots = k;
@@ -137,7 +142,7 @@ __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max
             pivots = k;
             return SX_UNBOUNDED;
         }
-        if (k >= budget) {
+        if (k - k0 >= budget) {
             pivots = k;
             return SX_EVICTED;
         }
@@ -248,21 +253,32 @@ struct TwoPhase {
 
 // orc_two_phase of the problem at src in the working set w, into the TwoPhase t; v, i, rv, ri are
 // the reduction scratch wg_solve takes.  Every path ends behind a barrier, so T, d and base are
-// complete afterwards.  Uniform over the workgroup.  Expanded in the kernel's body and not a function: the workgroup size inside the three __syncthreads_or of a problem is folded to the
+// complete afterwards.  Uniform over the workgroup.  Expanded in the kernel's body and not a
+// function: the workgroup size inside the three __syncthreads_or of a problem is folded to the
 // launch's only where they reach the kernel as three separate sites.
-#define WG_TWO_PHASE(t, w, src, by_col, max_pivots, budget, v, i, rv, ri)                           \
-    do {                                                                                            \
-        const int Ns_ = 1 + (w).n + (w).m, N1_ = Ns_ + (w).m;                                       \
-        wg_build(w, src, by_col);                                                                   \
-        wg_update_objective(w, N1_);                                                                \
-        (t).p1 = (t).p2 = 0;                                                                        \
-        (t).status = wg_classify(w, wg_solve(w, N1_, max_pivots, budget, (t).p1, v, i, rv, ri));    \
-        (t).ph2 = (t).status == SX_FEASIBLE;                                                        \
-        if ((t).ph2) {                                                                              \
-            wg_phase2_costs(w, src);                                                                \
-            wg_update_objective(w, Ns_);                                                            \
-            (t).status = wg_solve(w, Ns_, max_pivots, budget, (t).p2, v, i, rv, ri);                \
-        }                                                                                           \
+// Its two parts are entry points of their own for a saved state (k_batch_solve_st), which passes
+// the pivots a phase has behind it where the fresh solve passes the literal 0, which folds away:
+// WG_PHASE1 -- phase 1 at width N1 on a row that is already canonical, and what it decided;
+#define WG_PHASE1(t, w, N1, max_pivots, budget, k1, v, i, rv, ri)                                      \
+    do {                                                                                               \
+        (t).status = wg_classify(w, wg_solve(w, N1, max_pivots, budget, k1, (t).p1, v, i, rv, ri));    \
+        (t).ph2 = (t).status == SX_FEASIBLE;                                                           \
+    } while (0)
+// WG_PHASE2 -- phase 2 at width Ns on a canonical row.
+#define WG_PHASE2(t, w, Ns, max_pivots, budget, k2, v, i, rv, ri) \
+    (t).status = wg_solve(w, Ns, max_pivots, budget, k2, (t).p2, v, i, rv, ri)
+#define WG_TWO_PHASE(t, w, src, by_col, max_pivots, budget, v, i, rv, ri)        \
+    do {                                                                         \
+        const int Ns_ = 1 + (w).n + (w).m, N1_ = Ns_ + (w).m;                    \
+        wg_build(w, src, by_col);                                                \
+        wg_update_objective(w, N1_);                                             \
+        (t).p1 = (t).p2 = 0;                                                     \
+        WG_PHASE1(t, w, N1_, max_pivots, budget, 0LL, v, i, rv, ri);             \
+        if ((t).ph2) {                                                           \
+            wg_phase2_costs(w, src);                                             \
+            wg_update_objective(w, Ns_);                                         \
+            WG_PHASE2(t, w, Ns_, max_pivots, budget, 0LL, v, i, rv, ri);         \
+        }                                                                        \
     } while (0)
 
 // simplex_solve_batch: ragged problems packed by the host (A column-major, then b, then c), the RHS
@@ -464,6 +480,150 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_rag(BatchRagArgs a) {
     }
 }
 
+// simplex_solve_batch_device_state: k_batch_solve_dev with a saved state per problem (sx_common.hpp
+// BatchState: the stored columns of T dense at stride 1 + n + m, d at full width, the basis, the phase
+// and both pivot counts).  Without a.in a problem is built and solved as there; with it the working
+// set is loaded from the state instead and the same loop is re-entered -- phase 1 behind its saved
+// pivots, then phase 2 from 0 with the call's costs; or phase 2 behind its saved pivots, or, with
+// a.recost, from 0 on the row of the call's costs made canonical for the saved basis.  No outcome
+// has a case of its own: selection writes nothing, so a state whose phase had ended ends again
+// without a pivot.  The state's phase, pivot counts and basis are tested before anything is indexed
+// with them; a problem that fails gets SX_BAD_STATE and cleared outputs.  Behind the device entry's
+// epilogue the working set is written to a.out (which may be a.in: the workgroup has loaded all of
+// its problem by then).
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    __shared__ double s_v[16];
+    __shared__ int s_i[16];
+    __shared__ double s_rv;
+    __shared__ int s_ri;
+    __shared__ unsigned s_k;
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    const BatchWork w = wg_carve(W, n, m);
+    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+    // wg_by_col's rule, decided once: the strides are the launch's
+    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    const bool resume = a.in.T != nullptr;
+    const int cells = m * Ns;  // (a working set holds them, so they fit an int)
+    for (;;) {
+        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
+        __syncthreads();
+        const unsigned k = s_k;
+        if (k >= (unsigned)a.count) return;
+        // a resume reads only c
+        const SxSource src{resume ? nullptr : a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc,
+                           resume ? nullptr : a.b + (long long)k * a.b_sb, a.b_si, a.c + (long long)k * a.c_sb, a.c_sj};
+        TwoPhase t{SX_BAD_STATE, false, 0, 0};
+        bool good = true;
+        if (!resume) {
+            wg_build(w, src, by_col);
+            wg_update_objective(w, N1);
+        } else {
+            const int ph = a.in.phase[k];
+            const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
+            good = (ph == 1 || ph == 2) && q1 >= 0 && q2 >= 0;
+            if (good) {
+                // the basis indexes d (and, through the alias, T): phase 2 knows no artificial variable
+                const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m) : (unsigned)(n + m);
+                const int *base_in = a.in.base + (size_t)k * (size_t)m;
+                int bad = 0;
+                for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                    const int bi = base_in[i];
+                    w.base[i] = bi;
+                    bad |= (unsigned)bi >= lim;
+                }
+                good = !__syncthreads_or(bad);
+            }
+            if (good) {
+                // consecutive lanes walk the dense rows; the working set's stride is the odd ld
+                const double *T_in = a.in.T + (size_t)k * (size_t)cells;
+                for (int x = threadIdx.x; x < cells; x += SX_TILE) {
+                    const int i = x / Ns;
+                    w.T[(size_t)i * w.ld + (x - i * Ns)] = T_in[x];
+                }
+                const double *d_in = a.in.d + (size_t)k * (size_t)N1;
+                for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = d_in[j];
+                __syncthreads();
+                t.p1 = q1;
+                t.p2 = q2;
+                t.ph2 = ph == 2;
+            }
+        }
+        if (good) {
+            if (!t.ph2) {
+                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, s_v, s_i, &s_rv, &s_ri);
+                if (t.ph2) {
+                    wg_phase2_costs(w, src);
+                    wg_update_objective(w, Ns);
+                    t.p2 = 0;
+                }
+            } else if (a.recost) {
+                // the warm start: the call's costs on the saved tableau, the objective from +0.0
+                if (threadIdx.x == 0) w.d[0] = 0.0;
+                wg_phase2_costs(w, src);
+                wg_update_objective(w, Ns);
+                t.p2 = 0;
+            }
+            if (t.ph2) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, s_v, s_i, &s_rv, &s_ri);
+        }
+        // k_batch_solve_dev's epilogue; a problem whose state failed the tests has every output cleared
+        const bool feasible = t.status == SX_FEASIBLE, evicted = t.status == SX_EVICTED;
+        if (a.x != nullptr) {
+            for (int j = threadIdx.x; j < n; j += SX_TILE) w.prow[j] = 0.0;
+            __syncthreads();
+            if (feasible)
+                for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                    const unsigned bi = (unsigned)w.base[i];
+                    if (bi < (unsigned)n) w.prow[bi] = w.T[(size_t)i * w.ld];
+                }
+            __syncthreads();
+            double *x = a.x + (size_t)k * (size_t)n;
+            for (int j = threadIdx.x; j < n; j += SX_TILE) x[j] = w.prow[j];
+        }
+        if (a.base != nullptr) {
+            int *base_out = a.base + (size_t)k * (size_t)m;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = good ? w.base[i] : -1;
+        }
+        const int width = evicted || !good ? 0 : t.ph2 ? Ns : N1;
+        if (a.objrow != nullptr) {
+            double *row = a.objrow + (size_t)k * (size_t)N1;
+            for (int j = threadIdx.x; j < N1; j += SX_TILE) row[j] = j < width ? w.d[j] : 0.0;
+        }
+        if (threadIdx.x == 0) {
+            a.status[k] = evicted ? SX_NOT_ENDED : t.status;
+            a.pivots[2 * (size_t)k] = t.p1;
+            a.pivots[2 * (size_t)k + 1] = t.p2;
+            a.opt[k] = feasible ? w.d[0] : __builtin_nan("");
+            if (a.row_width != nullptr) a.row_width[k] = width;
+            if (evicted) atomicAdd(a.evicted, 1);
+        }
+        // the state: what phase 2 leaves behind its row in d is stale phase-1 data and is not kept
+        if (a.out.T != nullptr) {
+            if (good) {
+                double *T_out = a.out.T + (size_t)k * (size_t)cells;
+                for (int x = threadIdx.x; x < cells; x += SX_TILE) {
+                    const int i = x / Ns;
+                    T_out[x] = w.T[(size_t)i * w.ld + (x - i * Ns)];
+                }
+                double *d_out = a.out.d + (size_t)k * (size_t)N1;
+                for (int j = threadIdx.x; j < N1; j += SX_TILE) d_out[j] = t.ph2 && j >= Ns ? 0.0 : w.d[j];
+                int *base_out = a.out.base + (size_t)k * (size_t)m;
+                for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = w.base[i];
+            }
+            if (threadIdx.x == 0) {
+                a.out.phase[k] = !good ? 0 : t.ph2 ? 2 : 1;
+                if (good) {
+                    a.out.pivots[2 * (size_t)k] = t.p1;
+                    a.out.pivots[2 * (size_t)k + 1] = t.p2;
+                }
+            }
+        }
+        __syncthreads();  // the next problem overwrites the working set and s_k
+    }
+}
+
 // One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
 template <class Args, void (*KL)(Args), void (*KW)(Args)>
 struct Entry {
@@ -496,6 +656,7 @@ struct Entry {
 using HostEntry = Entry<BatchArgs, k_batch_solve<true>, k_batch_solve<false>>;
 using DevEntry = Entry<BatchDevArgs, k_batch_solve_dev<true>, k_batch_solve_dev<false>>;
 using RagEntry = Entry<BatchRagArgs, k_batch_solve_rag<true>, k_batch_solve_rag<false>>;
+using StEntry = Entry<BatchStArgs, k_batch_solve_st<true>, k_batch_solve_st<false>>;
 
 }  // namespace
 
@@ -511,4 +672,8 @@ void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t
 int sx_batch_resident_rag(bool lds, size_t lds_bytes) { return RagEntry::resident(lds, lds_bytes); }
 void sx_launch_batch_solve_rag(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     RagEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+int sx_batch_resident_st(bool lds, size_t lds_bytes) { return StEntry::resident(lds, lds_bytes); }
+void sx_launch_batch_solve_st(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    StEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

@@ -18,6 +18,7 @@
 #define SX_PIVOT_CAP (-11)     // opt-in pivot budget reached (off in parity mode)
 #define SX_NUMERIC_FAIL (-12)  // ratio argmin returned no row although a pivot is eligible
 #define SX_BAD_SHAPE (-14)     // ragged device batch: a problem's dimensions lie outside the envelope (-13: SX_HANG)
+#define SX_BAD_STATE (-15)     // state entry: a problem's saved state fails the kernel's checks
 
 #define SX_TILE 512     // argmin tile = reference THREADS (reduction.cu:6)
 #define SX_EPS 1e-9     // macro.h:28
@@ -438,6 +439,19 @@ struct BatchRagArgs : BatchDevArgs {
     const int *order;      // [count] device or null (identity): the work counter's value -> problem
     long long set;         // doubles of the envelope's working set, sx_batch_lay(n, m).total
 };
+// The state entry (simplex_solve_batch_device_state): BatchDevArgs plus the saved states it loads
+// and writes.  A state is dense per problem: T [m][1 + n + m] (the stored columns b | structural |
+// slack), d [1 + n + 2m], base [m], phase (1, 2; 0: none) and pivots [2].
+struct BatchState {
+    double *T, *d;
+    int *base, *phase;
+    long long *pivots;
+};
+struct BatchStArgs : BatchDevArgs {
+    BatchState in;   // T null: a fresh solve from A, b, c; else only c is read
+    BatchState out;  // T null: the state is not kept; may equal `in` member for member
+    int recost;      // a phase-2 state restarts phase 2 on the call's costs
+};
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
@@ -448,3 +462,5 @@ int sx_batch_resident_rag(bool lds, size_t lds_bytes);  // ... of the ragged dev
 void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve_rag(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+int sx_batch_resident_st(bool lds, size_t lds_bytes);  // ... of the state entry's kernel
+void sx_launch_batch_solve_st(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s);

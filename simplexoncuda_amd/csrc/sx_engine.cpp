@@ -2578,6 +2578,64 @@ int simplex_solve_batch_device(const simplex_batch_device_t *args) {
     return 0;
 }
 
+// The state entry: simplex_solve_batch_device with a saved state per problem, loaded from `in` and
+// written to `out` by the kernel (k_batch_solve_st).  The same two memsets and one launch, and none
+// of g_bb; a state's contents are device data, so the kernel tests them (SX_BAD_STATE).  As in the
+// ragged entry, every return code that needs no residency figure is decided before the first runtime
+// call, and the grid is no larger than what simplex_batch_device_workspace(n, m, count) paid for.
+static bool state_complete(const simplex_batch_state_t *s) {
+    return s->T != nullptr && s->d != nullptr && s->base != nullptr && s->phase != nullptr && s->pivots != nullptr;
+}
+
+int simplex_solve_batch_device_state(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                     const simplex_batch_state_t *out, int recost) {
+    if (args == nullptr || args->count < 0) return -1;
+    const int n = args->n, m = args->m, count = args->count;
+    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
+    if (cls == 0) return -3;
+    if (count == 0) return 0;
+    if (args->status == nullptr || args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr)
+        return -2;
+    if ((in != nullptr && !state_complete(in)) || (out != nullptr && !state_complete(out))) return -2;
+    if (in == nullptr) {
+        const SxSource src{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj};
+        const int rc = device_source_check(n, m, src, true, count, args->A_sb, args->b_sb, args->c_sb);
+        if (rc != 0) return rc;
+    } else {  // a resume reads only c
+        if (args->c == nullptr) return -2;
+        if ((count > 1 && args->c_sb == 0) || (n > 1 && args->c_sj == 0)) return -4;
+    }
+    if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0 ||
+        args->workspace_bytes < SX_BATCH_DEV_HEADER)
+        return -5;
+    const long long set = sx_batch_lay(n, m).total;
+    int grid = std::min(count, sx_batch_resident_st(cls == 2, (size_t)set * sizeof(double)));
+    if (cls == 1) {
+        const int slices = batch_device_grid(n, m, count, cls);  // what the workspace query counted
+        if (args->workspace_bytes < SX_BATCH_DEV_HEADER + (long long)slices * set * (long long)sizeof(double)) return -5;
+        grid = std::min(grid, slices);
+    }
+
+    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    BatchStArgs a{{n, m, count,
+                   args->A, args->A_sb, args->A_sr, args->A_sc, args->b, args->b_sb, args->b_si, args->c, args->c_sb,
+                   args->c_sj, args->max_pivots, g_batch_budget,
+                   args->status, args->pivots, args->opt, args->x, args->base, args->objrow, args->row_width,
+                   args->evicted, static_cast<unsigned *>(args->workspace)},
+                  in ? BatchState{in->T, in->d, in->base, in->phase, in->pivots} : none,
+                  out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
+                  recost != 0};
+    if (cls == 1) {
+        a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
+        a.slice = set;
+    }
+    hipStream_t s = static_cast<hipStream_t>(args->stream);
+    SX_HIP(hipMemsetAsync(args->workspace, 0, SX_BATCH_DEV_HEADER, s));
+    SX_HIP(hipMemsetAsync(args->evicted, 0, sizeof(int), s));
+    sx_launch_batch_solve_st(cls == 2, a, grid, (size_t)set * sizeof(double), s);
+    return 0;
+}
+
 // The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
 // The launch is the envelope's: its class, its working set (LDS bytes or slice), and a grid no
 // larger than simplex_batch_device_workspace(n, m, count) paid for.  The per-problem dimensions are
