@@ -307,6 +307,48 @@ def _default_ragged_order(n_active, m_active):
     return torch.argsort(m_k * (1 + n_k + m_k), descending=True, stable=True).to(torch.int32)
 
 
+def _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare):
+    """What solve_batch_tensors and resume_batch_tensors share, under torch.cuda.device(dev): the
+    output tensors, then prepare() -- the caller's own allocations; it returns the C entry's name and
+    that entry's arguments behind the BatchDeviceT -- then the workspace and the call itself.
+    source: the BatchDeviceT fields of the problems' data.  Returns BatchTensors' first eight fields."""
+    import torch
+
+    lib = _lib.load()
+    N1 = 1 + n + 2 * m
+    with torch.cuda.device(dev):
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        pivots = torch.empty((B, 2), dtype=torch.int64, device=dev)
+        opt = torch.empty(B, dtype=torch.float64, device=dev)
+        x = torch.empty((B, n), dtype=torch.float64, device=dev)
+        base = torch.empty((B, m), dtype=torch.int32, device=dev)
+        row = torch.empty((B, N1), dtype=torch.float64, device=dev) if objective_row else None
+        width = torch.empty(B, dtype=torch.int32, device=dev) if objective_row else None
+        evicted = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int32, device=dev)  # (the call zeroes it)
+        entry, extra = prepare()
+        if B > 0:
+            ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
+            if ws_bytes < 0:
+                raise ValueError(f"simplex_batch_device_workspace: bad arguments ({ws_bytes})")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            args = _lib.BatchDeviceT(
+                n=n, m=m, count=B, max_pivots=max_pivots,
+                status=status.data_ptr(), pivots=pivots.data_ptr(), opt=opt.data_ptr(), x=x.data_ptr(),
+                base=base.data_ptr(), objrow=row.data_ptr() if objective_row else None,
+                row_width=width.data_ptr() if objective_row else None, evicted=evicted.data_ptr(),
+                workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
+                stream=torch.cuda.current_stream(dev).cuda_stream, **source)
+            rc = getattr(lib, entry)(ctypes.byref(args), *extra)
+            if rc < 0:
+                raise ValueError(f"{entry}: bad arguments ({rc})")
+    return status, pivots, opt, x, base, row, width, evicted
+
+
+def _evicted_count(evicted, B):
+    """the launch's evicted count on the host: one 4-byte copy, which waits for the stream"""
+    return int(evicted.item()) if B > 0 else 0
+
+
 def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True, n_active=None, m_active=None,
                         order=None, keep_state=False):
     """twoPhaseMethodEx of B problems of one shape held in device tensors (simplex_solve_batch_device):
@@ -354,18 +396,11 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     if keep_state and ragged:
         raise ValueError("solve_batch_tensors: keep_state is not combined with a ragged call (n_active, m_active)")
     _check_device_placement("solve_batch_tensors", A, b, c)
-    lib = _lib.load()
     dev = A.device
-    N1 = 1 + n + 2 * m
-    with torch.cuda.device(dev):
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        pivots = torch.empty((B, 2), dtype=torch.int64, device=dev)
-        opt = torch.empty(B, dtype=torch.float64, device=dev)
-        x = torch.empty((B, n), dtype=torch.float64, device=dev)
-        base = torch.empty((B, m), dtype=torch.int32, device=dev)
-        row = torch.empty((B, N1), dtype=torch.float64, device=dev) if objective_row else None
-        width = torch.empty(B, dtype=torch.int32, device=dev) if objective_row else None
-        evicted = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int32, device=dev)  # (the call zeroes it)
+    state = None
+
+    def prepare():
+        nonlocal n_active, m_active, order, state
         if ragged:
             n_active = torch.full((B,), n, dtype=torch.int32, device=dev) if n_active is None else n_active.contiguous()
             m_active = torch.full((B,), m, dtype=torch.int32, device=dev) if m_active is None else m_active.contiguous()
@@ -373,41 +408,22 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
                 order = _default_ragged_order(n_active, m_active)
             elif order is not False:
                 order = order.contiguous()
-        state = BatchState.empty(B, n, m, dev) if keep_state else None
-        if B > 0:
-            ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
-            if ws_bytes < 0:
-                raise ValueError(f"simplex_batch_device_workspace: bad arguments ({ws_bytes})")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            args = _lib.BatchDeviceT(
-                n=n, m=m, count=B,
-                A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
-                b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
-                c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1),
-                max_pivots=max_pivots,
-                status=status.data_ptr(), pivots=pivots.data_ptr(), opt=opt.data_ptr(), x=x.data_ptr(),
-                base=base.data_ptr(), objrow=row.data_ptr() if objective_row else None,
-                row_width=width.data_ptr() if objective_row else None, evicted=evicted.data_ptr(),
-                workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
-                stream=torch.cuda.current_stream(dev).cuda_stream)
-            if ragged:
-                rc = lib.simplex_solve_batch_device_ragged(ctypes.byref(args), n_active.data_ptr(), m_active.data_ptr(),
-                                                           None if order is False else order.data_ptr())
-                if rc < 0:
-                    raise ValueError(f"simplex_solve_batch_device_ragged: bad arguments ({rc})")
-            elif keep_state:
-                rc = lib.simplex_solve_batch_device_state(ctypes.byref(args), None, ctypes.byref(state._struct()), 0)
-                if rc < 0:
-                    raise ValueError(f"simplex_solve_batch_device_state: bad arguments ({rc})")
-            else:
-                rc = lib.simplex_solve_batch_device(ctypes.byref(args))
-                if rc < 0:
-                    raise ValueError(f"simplex_solve_batch_device: bad arguments ({rc})")
-        out = BatchTensors(status, pivots, opt, x, base, row, width, evicted,
-                           n_active if ragged else None, m_active if ragged else None, state)
-        if not finish:
-            return out
-        out.evicted = int(evicted.item()) if B > 0 else 0
+            return "simplex_solve_batch_device_ragged", (n_active.data_ptr(), m_active.data_ptr(),
+                                                         None if order is False else order.data_ptr())
+        if keep_state:
+            state = BatchState.empty(B, n, m, dev)
+            return "simplex_solve_batch_device_state", (None, ctypes.byref(state._struct()), 0)
+        return "simplex_solve_batch_device", ()
+
+    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
+                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
+                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
+    out = BatchTensors(*outputs, n_active if ragged else None, m_active if ragged else None, state)
+    if not finish:
+        return out
+    with torch.cuda.device(dev):
+        out.evicted = _evicted_count(out.evicted, B)
         if out.evicted and not keep_state:
             _finish_evicted(out, A, b, c, max_pivots)
     return out
@@ -458,37 +474,20 @@ def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=Fa
         raise ValueError(f"resume_batch_tensors: the state is on {dev}; it must be on a GPU")
     if c.device != dev:
         raise ValueError(f"resume_batch_tensors: c is on {c.device}; it must be on the state's device, {dev}")
-    lib = _lib.load()
-    N1 = 1 + n + 2 * m
-    with torch.cuda.device(dev):
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        pivots = torch.empty((B, 2), dtype=torch.int64, device=dev)
-        opt = torch.empty(B, dtype=torch.float64, device=dev)
-        x = torch.empty((B, n), dtype=torch.float64, device=dev)
-        base = torch.empty((B, m), dtype=torch.int32, device=dev)
-        row = torch.empty((B, N1), dtype=torch.float64, device=dev) if objective_row else None
-        width = torch.empty(B, dtype=torch.int32, device=dev) if objective_row else None
-        evicted = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int32, device=dev)  # (the call zeroes it)
-        new = state if in_place else BatchState.empty(B, n, m, dev)
-        if B > 0:
-            ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
-            if ws_bytes < 0:
-                raise ValueError(f"simplex_batch_device_workspace: bad arguments ({ws_bytes})")
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            args = _lib.BatchDeviceT(
-                n=n, m=m, count=B, c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1), max_pivots=max_pivots,
-                status=status.data_ptr(), pivots=pivots.data_ptr(), opt=opt.data_ptr(), x=x.data_ptr(),
-                base=base.data_ptr(), objrow=row.data_ptr() if objective_row else None,
-                row_width=width.data_ptr() if objective_row else None, evicted=evicted.data_ptr(),
-                workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
-                stream=torch.cuda.current_stream(dev).cuda_stream)
-            rc = lib.simplex_solve_batch_device_state(ctypes.byref(args), ctypes.byref(state._struct()),
-                                                      ctypes.byref(new._struct()), 1 if recost else 0)
-            if rc < 0:
-                raise ValueError(f"simplex_solve_batch_device_state: bad arguments ({rc})")
-        out = BatchTensors(status, pivots, opt, x, base, row, width, evicted, None, None, new)
-        if finish:
-            out.evicted = int(evicted.item()) if B > 0 else 0
+    new = state
+
+    def prepare():
+        nonlocal new
+        if not in_place:
+            new = BatchState.empty(B, n, m, dev)
+        return "simplex_solve_batch_device_state", (ctypes.byref(state._struct()), ctypes.byref(new._struct()),
+                                                    1 if recost else 0)
+
+    source = dict(c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
+    out = BatchTensors(*outputs, None, None, new)
+    if finish:
+        out.evicted = _evicted_count(out.evicted, B)
     return out
 
 

@@ -22,6 +22,10 @@
 // k_batch_solve_rag (simplex_solve_batch_device_ragged: the same with per-problem dimensions
 // inside one envelope shape) and k_batch_solve_st (simplex_solve_batch_device_state: k_batch_solve_dev
 // that can load a problem's working set from a saved state and write it to one).
+// What surrounds the method is written once where that costs no time: every kernel names its static
+// LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
+// entries end with the same epilogue, wg_write_results, which writes a problem's results into the
+// caller's dense arrays; k_batch_solve_rag keeps that epilogue written out over its envelope.
 
 #include <float.h>
 
@@ -39,12 +43,38 @@ struct BatchWork {
     int n, m, ld;
 };
 
+// The kernels' static LDS: the reduction scratch of block_argmin512 / stage2_512, the argmin's result
+// and the work counter's value.  WG_SCRATCH declares them in a kernel and names them through one
+// WgScratch, which is what wg_next, wg_argmin, wg_solve and the macros take.  They stay five
+// __shared__ objects: as members of one object the address of i[] is derived from that of v[] in
+// every reduction step, and k_batch_solve measured 1.3-2 % slower.
+struct WgScratch {
+    double *v;  // [16]
+    int *i;     // [16]
+    double &rv;
+    int &ri;
+    unsigned &k;
+};
+#define WG_SCRATCH(sc)          \
+    __shared__ double s_v[16];  \
+    __shared__ int s_i[16];     \
+    __shared__ double s_rv;     \
+    __shared__ int s_ri;        \
+    __shared__ unsigned s_k;    \
+    const WgScratch sc { s_v, s_i, s_rv, s_ri, s_k }
+
+// the launch's next problem: thread 0 draws the work counter, every thread gets the value
+__device__ __forceinline__ unsigned wg_next(unsigned *counter, const WgScratch &sc) {
+    if (threadIdx.x == 0) sc.k = atomicAdd(counter, 1u);
+    __syncthreads();
+    return sc.k;
+}
+
 // orc_argmin over val(0) .. val(L - 1): per 512-wide tile the per-thread grid-stride pre-combine and
 // block_argmin512, then pass 2 over the tile winners when there is more than one tile.  The
 // workgroup walks the tiles one after the other.  Result in every thread.
 template <class F>
-__device__ __forceinline__ void wg_argmin(int L, F val, TilePart *parts, double *s_v, int *s_i, double *s_rv,
-                                          int *s_ri, double &v_out, int &i_out) {
+__device__ __forceinline__ void wg_argmin(int L, F val, TilePart *parts, const WgScratch &sc, double &v_out, int &i_out) {
     const int tiles = L > SX_TILE ? (L + SX_TILE - 1) / SX_TILE : 1;
     for (int b = 0; b < tiles; ++b) {
         double v = DBL_MAX;
@@ -56,11 +86,11 @@ __device__ __forceinline__ void wg_argmin(int L, F val, TilePart *parts, double 
                 i = idx;
             }
         }
-        block_argmin512(v, i, s_v, s_i);
+        block_argmin512(v, i, sc.v, sc.i);
         if (threadIdx.x == 0) {
             if (tiles == 1) {
-                *s_rv = v;
-                *s_ri = i;
+                sc.rv = v;
+                sc.ri = i;
             } else {
                 parts[b].v = v;
                 parts[b].idx = i;
@@ -72,15 +102,15 @@ __device__ __forceinline__ void wg_argmin(int L, F val, TilePart *parts, double 
     if (tiles > 1) {
         double v;
         int i;
-        stage2_512(parts, tiles, v, i, s_v, s_i);
+        stage2_512(parts, tiles, v, i, sc.v, sc.i);
         if (threadIdx.x == 0) {
-            *s_rv = v;
-            *s_ri = i;
+            sc.rv = v;
+            sc.ri = i;
         }
         __syncthreads();
     }
-    v_out = *s_rv;
-    i_out = *s_ri;
+    v_out = sc.rv;
+    i_out = sc.ri;
 }
 
 // orc_update_objective at width N: coef[i] = d[1 + base[i]] snapshot (kept in colE), then per column
@@ -109,8 +139,7 @@ __device__ __forceinline__ void wg_update_objective(const BatchWork &w, int N) {
 // tests and in front of the first write to T, d or base, so an eviction leaves what a cap at the
 // same count leaves.  A fresh solve passes the literal 0 for k0.  Uniform over the workgroup.
 __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max_pivots, long long budget,
-                                        long long k0, long long &pivots, double *s_v, int *s_i, double *s_rv,
-                                        int *s_ri) {
+                                        long long k0, long long &pivots, const WgScratch &sc) {
     const int n = w.n, m = w.m, ld = w.ld, Ns = 1 + n + m, art0 = Ns;
     // the row update gives each row to 16, 32 or 64 consecutive lanes (a row sweep by consecutive
     // lanes is conflict-free at any stride; narrow tableaux keep more rows in flight)
@@ -125,7 +154,7 @@ __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max
         }
         double dmin;
         int e;
-        wg_argmin(N - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, s_v, s_i, s_rv, s_ri, dmin, e);
+        wg_argmin(N - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, sc, dmin, e);
         if (!(cmp_eps(dmin, 0.0) < 0)) {
             pivots = k;
             return SX_FEASIBLE;
@@ -154,7 +183,7 @@ __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max
                 const double a = w.colE[i], b = w.T[(size_t)i * ld];
                 return cmp_eps(a, 0.0) > 0 ? b / a : DBL_MAX;
             },
-            w.parts, s_v, s_i, s_rv, s_ri, rv, r);
+            w.parts, sc, rv, r);
         if (r < 0 || r >= m) {
             pivots = k;
             return SX_NUMERIC_FAIL;
@@ -251,51 +280,90 @@ struct TwoPhase {
     long long p1, p2;
 };
 
-// orc_two_phase of the problem at src in the working set w, into the TwoPhase t; v, i, rv, ri are
-// the reduction scratch wg_solve takes.  Every path ends behind a barrier, so T, d and base are
+// orc_two_phase of the problem at src in the working set w, into the TwoPhase t; sc is the
+// kernel's WgScratch.  Every path ends behind a barrier, so T, d and base are
 // complete afterwards.  Uniform over the workgroup.  Expanded in the kernel's body and not a
 // function: the workgroup size inside the three __syncthreads_or of a problem is folded to the
 // launch's only where they reach the kernel as three separate sites.
 // Its two parts are entry points of their own for a saved state (k_batch_solve_st), which passes
 // the pivots a phase has behind it where the fresh solve passes the literal 0, which folds away:
 // WG_PHASE1 -- phase 1 at width N1 on a row that is already canonical, and what it decided;
-#define WG_PHASE1(t, w, N1, max_pivots, budget, k1, v, i, rv, ri)                                      \
-    do {                                                                                               \
-        (t).status = wg_classify(w, wg_solve(w, N1, max_pivots, budget, k1, (t).p1, v, i, rv, ri));    \
-        (t).ph2 = (t).status == SX_FEASIBLE;                                                           \
+#define WG_PHASE1(t, w, N1, max_pivots, budget, k1, sc)                                      \
+    do {                                                                                     \
+        (t).status = wg_classify(w, wg_solve(w, N1, max_pivots, budget, k1, (t).p1, sc));    \
+        (t).ph2 = (t).status == SX_FEASIBLE;                                                 \
     } while (0)
 // WG_PHASE2 -- phase 2 at width Ns on a canonical row.
-#define WG_PHASE2(t, w, Ns, max_pivots, budget, k2, v, i, rv, ri) \
-    (t).status = wg_solve(w, Ns, max_pivots, budget, k2, (t).p2, v, i, rv, ri)
-#define WG_TWO_PHASE(t, w, src, by_col, max_pivots, budget, v, i, rv, ri)        \
-    do {                                                                         \
-        const int Ns_ = 1 + (w).n + (w).m, N1_ = Ns_ + (w).m;                    \
-        wg_build(w, src, by_col);                                                \
-        wg_update_objective(w, N1_);                                             \
-        (t).p1 = (t).p2 = 0;                                                     \
-        WG_PHASE1(t, w, N1_, max_pivots, budget, 0LL, v, i, rv, ri);             \
-        if ((t).ph2) {                                                           \
-            wg_phase2_costs(w, src);                                             \
-            wg_update_objective(w, Ns_);                                         \
-            WG_PHASE2(t, w, Ns_, max_pivots, budget, 0LL, v, i, rv, ri);         \
-        }                                                                        \
+#define WG_PHASE2(t, w, Ns, max_pivots, budget, k2, sc) \
+    (t).status = wg_solve(w, Ns, max_pivots, budget, k2, (t).p2, sc)
+#define WG_TWO_PHASE(t, w, src, by_col, max_pivots, budget, sc)        \
+    do {                                                               \
+        const int Ns_ = 1 + (w).n + (w).m, N1_ = Ns_ + (w).m;          \
+        wg_build(w, src, by_col);                                      \
+        wg_update_objective(w, N1_);                                   \
+        (t).p1 = (t).p2 = 0;                                           \
+        WG_PHASE1(t, w, N1_, max_pivots, budget, 0LL, sc);             \
+        if ((t).ph2) {                                                 \
+            wg_phase2_costs(w, src);                                   \
+            wg_update_objective(w, Ns_);                               \
+            WG_PHASE2(t, w, Ns_, max_pivots, budget, 0LL, sc);         \
+        }                                                              \
     } while (0)
+
+// The one-shape device entries' epilogue (k_batch_solve_dev, k_batch_solve_st): problem k's results,
+// from the working set w and what the two-phase method left in t, into the caller's dense arrays
+// (BatchDevArgs), so nothing is left for the host.  A problem that failed its kernel's device-side
+// test (!good) has every output cleared.  Only __syncthreads() inside, so this is a function; it
+// ends without a barrier.  (k_batch_solve_rag keeps its own, over the envelope: DESIGN.md §10.2.)
+__device__ __forceinline__ void wg_write_results(const BatchDevArgs &a, const BatchWork &w, const TwoPhase &t, size_t k,
+                                                 bool good) {
+    const int n = w.n, m = w.m, Ns = 1 + n + m, N1 = Ns + m;
+    const bool feasible = t.status == SX_FEASIBLE, evicted = t.status == SX_EVICTED;
+    if (a.x != nullptr) {
+        // getSolutionHost, staged in the pivot-row copy (1 + n + m >= n doubles, free by now):
+        // zeros, then x[base[i]] = T[i][0] for the basic variables, written out by consecutive lanes
+        for (int j = threadIdx.x; j < n; j += SX_TILE) w.prow[j] = 0.0;
+        __syncthreads();
+        if (feasible)
+            for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                const unsigned bi = (unsigned)w.base[i];
+                if (bi < (unsigned)n) w.prow[bi] = w.T[(size_t)i * w.ld];
+            }
+        __syncthreads();
+        double *x = a.x + k * (size_t)n;
+        for (int j = threadIdx.x; j < n; j += SX_TILE) x[j] = w.prow[j];
+    }
+    if (a.base != nullptr) {
+        int *base_out = a.base + k * (size_t)m;
+        for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = good ? w.base[i] : -1;
+    }
+    // the row simplex_last_objective_row reports: phase 2's 1 + n + m entries once phase 2 was
+    // entered (what lies behind them in d is stale phase-1 data), else phase 1's full width;
+    // nothing of an evicted or cleared problem
+    const int width = evicted || !good ? 0 : t.ph2 ? Ns : N1;
+    if (a.objrow != nullptr) {
+        double *row = a.objrow + k * (size_t)N1;
+        for (int j = threadIdx.x; j < N1; j += SX_TILE) row[j] = j < width ? w.d[j] : 0.0;
+    }
+    if (threadIdx.x == 0) {
+        a.status[k] = evicted ? SX_NOT_ENDED : t.status;
+        a.pivots[2 * k] = t.p1;
+        a.pivots[2 * k + 1] = t.p2;
+        a.opt[k] = feasible ? w.d[0] : __builtin_nan("");
+        if (a.row_width != nullptr) a.row_width[k] = width;
+        if (evicted) atomicAdd(a.evicted, 1);
+    }
+}
 
 // simplex_solve_batch: ragged problems packed by the host (A column-major, then b, then c), the RHS
 // column, the basis and a BatchRes per problem written out for the host to finish.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE) void k_batch_solve(BatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    __shared__ double s_v[16];
-    __shared__ int s_i[16];
-    __shared__ double s_rv;
-    __shared__ int s_ri;
-    __shared__ unsigned s_k;
+    WG_SCRATCH(sc);
     double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
     for (;;) {
-        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
-        __syncthreads();
-        const unsigned k = s_k;
+        const unsigned k = wg_next(a.counter, sc);
         if (k >= (unsigned)a.count) return;
         const int id = a.order[k];
         const BatchProb pb = a.probs[id];
@@ -305,7 +373,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve(BatchArgs a) {
         const SxSource src{A, 1, m, bv, 1, bv + m, 1};
         const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
         TwoPhase t;
-        WG_TWO_PHASE(t, w, src, wg_by_col(src), a.max_pivots, budget, s_v, s_i, &s_rv, &s_ri);
+        WG_TWO_PHASE(t, w, src, wg_by_col(src), a.max_pivots, budget, sc);
         double *out = a.out + pb.out_off;
         int *base_out = reinterpret_cast<int *>(out + m);
         for (int i = threadIdx.x; i < m; i += SX_TILE) {
@@ -321,73 +389,32 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve(BatchArgs a) {
             r.evicted = t.status == SX_EVICTED ? 1 : 0;
             a.res[id] = r;
         }
-        __syncthreads();  // the next problem overwrites the working set and s_k
+        __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
 
 // simplex_solve_batch_device: every problem has the launch's one shape, problem k is the work
 // counter's value, A, b and c are read in place through the caller's element strides, and the
-// epilogue writes the caller's dense result arrays -- the solution scatter and the objective row
-// included -- so nothing is left for the host.
+// epilogue (wg_write_results) writes the caller's dense result arrays.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    __shared__ double s_v[16];
-    __shared__ int s_i[16];
-    __shared__ double s_rv;
-    __shared__ int s_ri;
-    __shared__ unsigned s_k;
+    WG_SCRATCH(sc);
     double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    const int n = a.n, m = a.m;
     const BatchWork w = wg_carve(W, n, m);
     const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
     // wg_by_col's rule, decided once: the strides are the launch's
     const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
     for (;;) {
-        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
-        __syncthreads();
-        const unsigned k = s_k;
+        const unsigned k = wg_next(a.counter, sc);
         if (k >= (unsigned)a.count) return;
         const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
                            a.c + (long long)k * a.c_sb, a.c_sj};
         TwoPhase t;
-        WG_TWO_PHASE(t, w, src, by_col, a.max_pivots, budget, s_v, s_i, &s_rv, &s_ri);
-        const bool feasible = t.status == SX_FEASIBLE, evicted = t.status == SX_EVICTED;
-        if (a.x != nullptr) {
-            // getSolutionHost, staged in the pivot-row copy (1 + n + m >= n doubles, free by now):
-            // zeros, then x[base[i]] = T[i][0] for the basic variables, written out by consecutive lanes
-            for (int j = threadIdx.x; j < n; j += SX_TILE) w.prow[j] = 0.0;
-            __syncthreads();
-            if (feasible)
-                for (int i = threadIdx.x; i < m; i += SX_TILE) {
-                    const unsigned bi = (unsigned)w.base[i];
-                    if (bi < (unsigned)n) w.prow[bi] = w.T[(size_t)i * w.ld];
-                }
-            __syncthreads();
-            double *x = a.x + (size_t)k * (size_t)n;
-            for (int j = threadIdx.x; j < n; j += SX_TILE) x[j] = w.prow[j];
-        }
-        if (a.base != nullptr) {
-            int *base_out = a.base + (size_t)k * (size_t)m;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = w.base[i];
-        }
-        // the row simplex_last_objective_row reports: phase 2's 1 + n + m entries once phase 2 was
-        // entered (what lies behind them in d is stale phase-1 data), else phase 1's full width;
-        // nothing of an evicted problem
-        const int width = evicted ? 0 : t.ph2 ? Ns : N1;
-        if (a.objrow != nullptr) {
-            double *row = a.objrow + (size_t)k * (size_t)N1;
-            for (int j = threadIdx.x; j < N1; j += SX_TILE) row[j] = j < width ? w.d[j] : 0.0;
-        }
-        if (threadIdx.x == 0) {
-            a.status[k] = evicted ? SX_NOT_ENDED : t.status;
-            a.pivots[2 * (size_t)k] = t.p1;
-            a.pivots[2 * (size_t)k + 1] = t.p2;
-            a.opt[k] = feasible ? w.d[0] : __builtin_nan("");
-            if (a.row_width != nullptr) a.row_width[k] = width;
-            if (evicted) atomicAdd(a.evicted, 1);
-        }
-        __syncthreads();  // the next problem overwrites the working set and s_k
+        WG_TWO_PHASE(t, w, src, by_col, a.max_pivots, budget, sc);
+        wg_write_results(a, w, t, k, true);
+        __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
 
@@ -401,24 +428,18 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_dev(BatchDevArgs a) {
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE) void k_batch_solve_rag(BatchRagArgs a) {
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    __shared__ double s_v[16];
-    __shared__ int s_i[16];
-    __shared__ double s_rv;
-    __shared__ int s_ri;
-    __shared__ unsigned s_k;
+    WG_SCRATCH(sc);
     double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
     const int n = a.n, m = a.m, N1 = 1 + n + 2 * m;
     // wg_by_col's rule, decided once: the strides are the launch's
     const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
     for (;;) {
-        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
-        __syncthreads();
-        const unsigned turn = s_k;
+        const unsigned turn = wg_next(a.counter, sc);
         if (turn >= (unsigned)a.count) return;
         // the problem and its dimensions are the same in every lane: kept in scalar registers
         const int k = __builtin_amdgcn_readfirstlane(a.order != nullptr ? a.order[turn] : (int)turn);
         if ((unsigned)k >= (unsigned)a.count) {  // not a problem of this call: skipped
-            __syncthreads();                     // (s_k is rewritten next)
+            __syncthreads();                     // (sc.k is rewritten next)
             continue;
         }
         const int nk = __builtin_amdgcn_readfirstlane(a.n_k[k]), mk = __builtin_amdgcn_readfirstlane(a.m_k[k]);
@@ -432,7 +453,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_rag(BatchRagArgs a) {
             const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(en, em);
             const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
                                a.c + (long long)k * a.c_sb, a.c_sj};
-            WG_TWO_PHASE(t, w, src, by_col, a.max_pivots, budget, s_v, s_i, &s_rv, &s_ri);
+            WG_TWO_PHASE(t, w, src, by_col, a.max_pivots, budget, sc);
         }
         const bool feasible = t.status == SX_FEASIBLE, evicted = t.status == SX_EVICTED;
         if (a.x != nullptr) {
@@ -476,7 +497,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_rag(BatchRagArgs a) {
             if (a.row_width != nullptr) a.row_width[k] = width;
             if (evicted) atomicAdd(a.evicted, 1);
         }
-        __syncthreads();  // the next problem overwrites the working set and s_k
+        __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
 
@@ -494,11 +515,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_rag(BatchRagArgs a) {
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    __shared__ double s_v[16];
-    __shared__ int s_i[16];
-    __shared__ double s_rv;
-    __shared__ int s_ri;
-    __shared__ unsigned s_k;
+    WG_SCRATCH(sc);
     double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
     const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
     const BatchWork w = wg_carve(W, n, m);
@@ -508,9 +525,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
     const bool resume = a.in.T != nullptr;
     const int cells = m * Ns;  // (a working set holds them, so they fit an int)
     for (;;) {
-        if (threadIdx.x == 0) s_k = atomicAdd(a.counter, 1u);
-        __syncthreads();
-        const unsigned k = s_k;
+        const unsigned k = wg_next(a.counter, sc);
         if (k >= (unsigned)a.count) return;
         // a resume reads only c
         const SxSource src{resume ? nullptr : a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc,
@@ -553,7 +568,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
         }
         if (good) {
             if (!t.ph2) {
-                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, s_v, s_i, &s_rv, &s_ri);
+                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
                 if (t.ph2) {
                     wg_phase2_costs(w, src);
                     wg_update_objective(w, Ns);
@@ -566,39 +581,10 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
                 wg_update_objective(w, Ns);
                 t.p2 = 0;
             }
-            if (t.ph2) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, s_v, s_i, &s_rv, &s_ri);
+            if (t.ph2) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
         }
-        // k_batch_solve_dev's epilogue; a problem whose state failed the tests has every output cleared
-        const bool feasible = t.status == SX_FEASIBLE, evicted = t.status == SX_EVICTED;
-        if (a.x != nullptr) {
-            for (int j = threadIdx.x; j < n; j += SX_TILE) w.prow[j] = 0.0;
-            __syncthreads();
-            if (feasible)
-                for (int i = threadIdx.x; i < m; i += SX_TILE) {
-                    const unsigned bi = (unsigned)w.base[i];
-                    if (bi < (unsigned)n) w.prow[bi] = w.T[(size_t)i * w.ld];
-                }
-            __syncthreads();
-            double *x = a.x + (size_t)k * (size_t)n;
-            for (int j = threadIdx.x; j < n; j += SX_TILE) x[j] = w.prow[j];
-        }
-        if (a.base != nullptr) {
-            int *base_out = a.base + (size_t)k * (size_t)m;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = good ? w.base[i] : -1;
-        }
-        const int width = evicted || !good ? 0 : t.ph2 ? Ns : N1;
-        if (a.objrow != nullptr) {
-            double *row = a.objrow + (size_t)k * (size_t)N1;
-            for (int j = threadIdx.x; j < N1; j += SX_TILE) row[j] = j < width ? w.d[j] : 0.0;
-        }
-        if (threadIdx.x == 0) {
-            a.status[k] = evicted ? SX_NOT_ENDED : t.status;
-            a.pivots[2 * (size_t)k] = t.p1;
-            a.pivots[2 * (size_t)k + 1] = t.p2;
-            a.opt[k] = feasible ? w.d[0] : __builtin_nan("");
-            if (a.row_width != nullptr) a.row_width[k] = width;
-            if (evicted) atomicAdd(a.evicted, 1);
-        }
+        // a problem whose state failed the tests has every output cleared
+        wg_write_results(a, w, t, k, good);
         // the state: what phase 2 leaves behind its row in d is stale phase-1 data and is not kept
         if (a.out.T != nullptr) {
             if (good) {
@@ -620,7 +606,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
                 }
             }
         }
-        __syncthreads();  // the next problem overwrites the working set and s_k
+        __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
 
@@ -660,20 +646,23 @@ using StEntry = Entry<BatchStArgs, k_batch_solve_st<true>, k_batch_solve_st<fals
 
 }  // namespace
 
-int sx_batch_resident(bool lds, size_t lds_bytes, bool dev) {
-    return dev ? DevEntry::resident(lds, lds_bytes) : HostEntry::resident(lds, lds_bytes);
+int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes) {
+    switch (entry) {
+    case BatchEntry::Dev: return DevEntry::resident(lds, lds_bytes);
+    case BatchEntry::Rag: return RagEntry::resident(lds, lds_bytes);
+    case BatchEntry::St: return StEntry::resident(lds, lds_bytes);
+    default: return HostEntry::resident(lds, lds_bytes);
+    }
 }
 void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     HostEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }
-void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+void sx_launch_batch_solve(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     DevEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }
-int sx_batch_resident_rag(bool lds, size_t lds_bytes) { return RagEntry::resident(lds, lds_bytes); }
-void sx_launch_batch_solve_rag(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+void sx_launch_batch_solve(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     RagEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }
-int sx_batch_resident_st(bool lds, size_t lds_bytes) { return StEntry::resident(lds, lds_bytes); }
-void sx_launch_batch_solve_st(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+void sx_launch_batch_solve(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     StEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

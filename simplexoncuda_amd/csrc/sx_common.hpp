@@ -455,12 +455,12 @@ struct BatchStArgs : BatchDevArgs {
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
-// workgroups of the batch kernel (dev: of the device-resident entry's kernel) the current device
-// holds at once with this much dynamic LDS
-int sx_batch_resident(bool lds, size_t lds_bytes, bool dev = false);
-int sx_batch_resident_rag(bool lds, size_t lds_bytes);  // ... of the ragged device entry's kernel
+// The four entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
+enum class BatchEntry { Host, Dev, Rag, St };
+// workgroups of that entry's kernel the current device holds at once with this much dynamic LDS
+int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes);
+// one launch of the entry the argument struct belongs to
 void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_bytes, hipStream_t s);
-void sx_launch_batch_solve_dev(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s);
-void sx_launch_batch_solve_rag(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s);
-int sx_batch_resident_st(bool lds, size_t lds_bytes);  // ... of the state entry's kernel
-void sx_launch_batch_solve_st(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s);

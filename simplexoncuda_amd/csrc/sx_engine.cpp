@@ -2463,11 +2463,11 @@ int simplex_solve_batch(problem_t *const *problems, int count, long long max_piv
                 a.ws = nullptr;
                 a.slice = 0;
                 const size_t lds = (size_t)big * sizeof(double);
-                sx_launch_batch_solve(true, a, std::min(a.count, sx_batch_resident(true, lds)), lds, nullptr);
+                sx_launch_batch_solve(true, a, std::min(a.count, sx_batch_resident(BatchEntry::Host, true, lds)), lds, nullptr);
             } else {
                 const size_t slice_bytes = (size_t)big * sizeof(double);
                 const long long fit = (long long)std::max<size_t>(1, SX_BATCH_WS_BYTES / slice_bytes);
-                const int grid = (int)std::min<long long>(std::min(a.count, sx_batch_resident(false, 0)), fit);
+                const int grid = (int)std::min<long long>(std::min(a.count, sx_batch_resident(BatchEntry::Host, false, 0)), fit);
                 batch_reserve(&g_bb.ws, &g_bb.ws_bytes, slice_bytes * (size_t)grid);
                 a.ws = static_cast<double *>(g_bb.ws);
                 a.slice = big;
@@ -2524,15 +2524,15 @@ int simplex_solve_batch(problem_t *const *problems, int count, long long max_piv
     return 0;
 }
 
-// The device-resident entry: uniform shape, device pointers in and out, the caller's stream and
-// workspace.  Nothing here allocates, copies or synchronises, and none of the state above (g_bb,
-// g_batch_mu, g_batch_counts) is touched: two memsets and one launch are enqueued.
+// The device-resident entries: device pointers in and out, the caller's stream and workspace.
+// Nothing here allocates, copies or synchronises, and none of the state above (g_bb, g_batch_mu,
+// g_batch_counts) is touched: two memsets and one launch are enqueued.
 // workspace: [SX_BATCH_DEV_HEADER bytes: the work counter] [class 1: one slice per workgroup]
 static int batch_device_grid(int n, int m, int count, int cls) {
     const size_t set = (size_t)sx_batch_lay(n, m).total * sizeof(double);
-    if (cls == 2) return std::min(count, sx_batch_resident(true, set, true));
+    if (cls == 2) return std::min(count, sx_batch_resident(BatchEntry::Dev, true, set));
     const long long fit = (long long)std::max<size_t>(1, SX_BATCH_WS_BYTES / set);
-    return (int)std::min<long long>(std::min(count, sx_batch_resident(false, 0, true)), fit);
+    return (int)std::min<long long>(std::min(count, sx_batch_resident(BatchEntry::Dev, false, 0)), fit);
 }
 
 long long simplex_batch_device_workspace(int n, int m, int count) {
@@ -2544,64 +2544,36 @@ long long simplex_batch_device_workspace(int n, int m, int count) {
            (long long)batch_device_grid(n, m, count, cls) * sx_batch_lay(n, m).total * (long long)sizeof(double);
 }
 
-int simplex_solve_batch_device(const simplex_batch_device_t *args) {
+// The body the three entries share.  batch_device_plan decides the return code and, for a call that
+// launches, fills the kernel's arguments and the launch's shape; batch_device_enqueue enqueues it.
+struct BatchDevPlan {
+    BatchDevArgs a;  // complete: ws and slice stay zero for the LDS class
+    bool lds;
+    int grid;        // 0: nothing to launch (count == 0)
+    size_t set_bytes;
+};
+
+// own_ok: the entry's own required pointers are there (n_k / m_k, complete states); c_only: a resume,
+// which reads neither A nor b.  Every code that needs no residency figure is decided before the first
+// runtime call, in this order: -1, -3, 0 for an empty call, -2, the source's own -2 / -4, -5 for the
+// workspace's address and header.  Then the grid: min(count, the entry's own residency) and, for class
+// 1, no more than the slices simplex_batch_device_workspace(n, m, count) counted, which workspace_bytes
+// must cover (-5).
+static int batch_device_plan(const simplex_batch_device_t *args, BatchEntry entry, bool own_ok, bool c_only,
+                             BatchDevPlan *p) {
+    p->grid = 0;
     if (args == nullptr || args->count < 0) return -1;
     const int n = args->n, m = args->m, count = args->count;
     const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
     if (cls == 0) return -3;
     if (count == 0) return 0;
-    if (args->status == nullptr || args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr)
+    if (args->status == nullptr || args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr || !own_ok)
         return -2;
-    const SxSource src{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj};
-    const int rc = device_source_check(n, m, src, true, count, args->A_sb, args->b_sb, args->c_sb);
-    if (rc != 0) return rc;
-    if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0) return -5;
-    const int grid = batch_device_grid(n, m, count, cls);
-    const long long set = sx_batch_lay(n, m).total;
-    const long long need = SX_BATCH_DEV_HEADER + (cls == 1 ? (long long)grid * set * (long long)sizeof(double) : 0);
-    if (args->workspace_bytes < need) return -5;
-
-    // in the struct's order, which is the caller's; ws and slice stay zero for the LDS class
-    BatchDevArgs a{n, m, count,
-                   args->A, args->A_sb, args->A_sr, args->A_sc, args->b, args->b_sb, args->b_si, args->c, args->c_sb, args->c_sj,
-                   args->max_pivots, g_batch_budget,
-                   args->status, args->pivots, args->opt, args->x, args->base, args->objrow, args->row_width, args->evicted,
-                   static_cast<unsigned *>(args->workspace)};
-    if (cls == 1) {
-        a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
-        a.slice = set;
-    }
-    hipStream_t s = static_cast<hipStream_t>(args->stream);
-    SX_HIP(hipMemsetAsync(args->workspace, 0, SX_BATCH_DEV_HEADER, s));
-    SX_HIP(hipMemsetAsync(args->evicted, 0, sizeof(int), s));
-    sx_launch_batch_solve_dev(cls == 2, a, grid, (size_t)set * sizeof(double), s);
-    return 0;
-}
-
-// The state entry: simplex_solve_batch_device with a saved state per problem, loaded from `in` and
-// written to `out` by the kernel (k_batch_solve_st).  The same two memsets and one launch, and none
-// of g_bb; a state's contents are device data, so the kernel tests them (SX_BAD_STATE).  As in the
-// ragged entry, every return code that needs no residency figure is decided before the first runtime
-// call, and the grid is no larger than what simplex_batch_device_workspace(n, m, count) paid for.
-static bool state_complete(const simplex_batch_state_t *s) {
-    return s->T != nullptr && s->d != nullptr && s->base != nullptr && s->phase != nullptr && s->pivots != nullptr;
-}
-
-int simplex_solve_batch_device_state(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
-                                     const simplex_batch_state_t *out, int recost) {
-    if (args == nullptr || args->count < 0) return -1;
-    const int n = args->n, m = args->m, count = args->count;
-    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
-    if (cls == 0) return -3;
-    if (count == 0) return 0;
-    if (args->status == nullptr || args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr)
-        return -2;
-    if ((in != nullptr && !state_complete(in)) || (out != nullptr && !state_complete(out))) return -2;
-    if (in == nullptr) {
+    if (!c_only) {
         const SxSource src{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj};
         const int rc = device_source_check(n, m, src, true, count, args->A_sb, args->b_sb, args->c_sb);
         if (rc != 0) return rc;
-    } else {  // a resume reads only c
+    } else {
         if (args->c == nullptr) return -2;
         if ((count > 1 && args->c_sb == 0) || (n > 1 && args->c_sj == 0)) return -4;
     }
@@ -2609,77 +2581,74 @@ int simplex_solve_batch_device_state(const simplex_batch_device_t *args, const s
         args->workspace_bytes < SX_BATCH_DEV_HEADER)
         return -5;
     const long long set = sx_batch_lay(n, m).total;
-    int grid = std::min(count, sx_batch_resident_st(cls == 2, (size_t)set * sizeof(double)));
+    p->lds = cls == 2;
+    p->set_bytes = (size_t)set * sizeof(double);
+    int grid = std::min(count, sx_batch_resident(entry, p->lds, p->set_bytes));
     if (cls == 1) {
         const int slices = batch_device_grid(n, m, count, cls);  // what the workspace query counted
         if (args->workspace_bytes < SX_BATCH_DEV_HEADER + (long long)slices * set * (long long)sizeof(double)) return -5;
         grid = std::min(grid, slices);
     }
-
-    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    BatchStArgs a{{n, m, count,
-                   args->A, args->A_sb, args->A_sr, args->A_sc, args->b, args->b_sb, args->b_si, args->c, args->c_sb,
-                   args->c_sj, args->max_pivots, g_batch_budget,
-                   args->status, args->pivots, args->opt, args->x, args->base, args->objrow, args->row_width,
-                   args->evicted, static_cast<unsigned *>(args->workspace)},
-                  in ? BatchState{in->T, in->d, in->base, in->phase, in->pivots} : none,
-                  out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
-                  recost != 0};
+    // in the struct's order, which is the caller's
+    p->a = BatchDevArgs{n, m, count,
+                        args->A, args->A_sb, args->A_sr, args->A_sc, args->b, args->b_sb, args->b_si, args->c, args->c_sb,
+                        args->c_sj, args->max_pivots, g_batch_budget,
+                        args->status, args->pivots, args->opt, args->x, args->base, args->objrow, args->row_width,
+                        args->evicted, static_cast<unsigned *>(args->workspace)};
     if (cls == 1) {
-        a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
-        a.slice = set;
+        p->a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
+        p->a.slice = set;
     }
-    hipStream_t s = static_cast<hipStream_t>(args->stream);
-    SX_HIP(hipMemsetAsync(args->workspace, 0, SX_BATCH_DEV_HEADER, s));
-    SX_HIP(hipMemsetAsync(args->evicted, 0, sizeof(int), s));
-    sx_launch_batch_solve_st(cls == 2, a, grid, (size_t)set * sizeof(double), s);
+    p->grid = grid;
     return 0;
 }
 
-// The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
-// The launch is the envelope's: its class, its working set (LDS bytes or slice), and a grid no
-// larger than simplex_batch_device_workspace(n, m, count) paid for.  The per-problem dimensions are
-// device data, so the kernel tests them (SX_BAD_SHAPE).  Every return code that needs no residency
-// figure is decided before the first runtime call; only class 1's workspace size needs one.
-int simplex_solve_batch_device_ragged(const simplex_batch_device_t *args, const int *n_k, const int *m_k,
-                                      const int *order) {
-    if (args == nullptr || args->count < 0) return -1;
-    const int n = args->n, m = args->m, count = args->count;
-    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
-    if (cls == 0) return -3;
-    if (count == 0) return 0;
-    if (n_k == nullptr || m_k == nullptr || args->status == nullptr || args->pivots == nullptr ||
-        args->opt == nullptr || args->evicted == nullptr)
-        return -2;
-    const SxSource src{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj};
-    const int rc = device_source_check(n, m, src, true, count, args->A_sb, args->b_sb, args->c_sb);
-    if (rc != 0) return rc;
-    if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0 ||
-        args->workspace_bytes < SX_BATCH_DEV_HEADER)
-        return -5;
-    const long long set = sx_batch_lay(n, m).total;
-    int grid = std::min(count, sx_batch_resident_rag(cls == 2, (size_t)set * sizeof(double)));
-    if (cls == 1) {
-        const int slices = batch_device_grid(n, m, count, cls);  // what the workspace query counted
-        if (args->workspace_bytes < SX_BATCH_DEV_HEADER + (long long)slices * set * (long long)sizeof(double)) return -5;
-        grid = std::min(grid, slices);
-    }
-
-    BatchRagArgs a{{n, m, count,
-                    args->A, args->A_sb, args->A_sr, args->A_sc, args->b, args->b_sb, args->b_si, args->c, args->c_sb,
-                    args->c_sj, args->max_pivots, g_batch_budget,
-                    args->status, args->pivots, args->opt, args->x, args->base, args->objrow, args->row_width,
-                    args->evicted, static_cast<unsigned *>(args->workspace)},
-                   n_k, m_k, order, set};
-    if (cls == 1) {
-        a.ws = reinterpret_cast<double *>(static_cast<unsigned char *>(args->workspace) + SX_BATCH_DEV_HEADER);
-        a.slice = set;
-    }
+extern "C++" template <class Args>  // (Args: BatchDevArgs or what wraps it)
+static int batch_device_enqueue(const simplex_batch_device_t *args, const BatchDevPlan &p, const Args &a) {
     hipStream_t s = static_cast<hipStream_t>(args->stream);
     SX_HIP(hipMemsetAsync(args->workspace, 0, SX_BATCH_DEV_HEADER, s));
     SX_HIP(hipMemsetAsync(args->evicted, 0, sizeof(int), s));
-    sx_launch_batch_solve_rag(cls == 2, a, grid, (size_t)set * sizeof(double), s);
+    sx_launch_batch_solve(p.lds, a, p.grid, p.set_bytes, s);
     return 0;
+}
+
+// The one-shape entry (k_batch_solve_dev).
+int simplex_solve_batch_device(const simplex_batch_device_t *args) {
+    BatchDevPlan p;
+    const int rc = batch_device_plan(args, BatchEntry::Dev, true, false, &p);
+    if (rc != 0 || p.grid == 0) return rc;
+    return batch_device_enqueue(args, p, p.a);
+}
+
+// The state entry: a saved state per problem, loaded from `in` and written to `out` by the kernel
+// (k_batch_solve_st).  A state's contents are device data, so the kernel tests them (SX_BAD_STATE).
+static bool state_complete(const simplex_batch_state_t *s) {
+    return s == nullptr ||
+           (s->T != nullptr && s->d != nullptr && s->base != nullptr && s->phase != nullptr && s->pivots != nullptr);
+}
+
+int simplex_solve_batch_device_state(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                     const simplex_batch_state_t *out, int recost) {
+    BatchDevPlan p;
+    const int rc = batch_device_plan(args, BatchEntry::St, state_complete(in) && state_complete(out), in != nullptr, &p);
+    if (rc != 0 || p.grid == 0) return rc;
+    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    return batch_device_enqueue(args, p,
+                                BatchStArgs{p.a, in ? BatchState{in->T, in->d, in->base, in->phase, in->pivots} : none,
+                                            out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
+                                            recost != 0});
+}
+
+// The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
+// The launch is the envelope's: its class, its working set (LDS bytes or slice).  The per-problem
+// dimensions are device data, so the kernel tests them (SX_BAD_SHAPE).
+int simplex_solve_batch_device_ragged(const simplex_batch_device_t *args, const int *n_k, const int *m_k,
+                                      const int *order) {
+    BatchDevPlan p;
+    const int rc = batch_device_plan(args, BatchEntry::Rag, n_k != nullptr && m_k != nullptr, false, &p);
+    if (rc != 0 || p.grid == 0) return rc;
+    const long long set = (long long)(p.set_bytes / sizeof(double));
+    return batch_device_enqueue(args, p, BatchRagArgs{p.a, n_k, m_k, order, set});
 }
 
 // ---------------------------------------------------------------- tabular_t API

@@ -1,7 +1,8 @@
 """What the C entries of the device paths accept and sx.solve_batch_tensors / sx.solve_tensors never
 pass (needs an MI355X), through the ctypes caller device_entries.py:
 
-  optional outputs     x, base, objrow, row_width NULL in every combination (both batch device entries);
+  optional outputs     x, base, objrow, row_width NULL in every combination (the three batch device entries,
+                       the state entry called fresh without and with a state to write);
                        x, base, objrow, opt_out, row_width_out NULL (simplex_solve_device) -- what is
                        passed equals the all-present call bit for bit, which equals the oracle
   negative strides     A reversed along rows, columns, both and the batch, b and c reversed, the base
@@ -17,6 +18,7 @@ import torch
 import device_entries as de
 import oracle
 import simplexoncuda_amd as sx
+import state_entry as se
 import test_gpu_batch_device as tbd
 import test_gpu_batch_ragged as rag
 import test_gpu_solve_device as tsd
@@ -53,14 +55,19 @@ def test_batch_optional_outputs(gpu, n, m, B):
         assert {r["status"] for r in refs} >= ({sx.FEASIBLE, sx.INFEASIBLE, sx.UNBOUNDED} if m == 31 else
                                                {sx.FEASIBLE, sx.UNBOUNDED})
     A, b, c = (de.dense(t) for t in tensors(insts))
-    for ragged in (False, True):
-        full = de.batch_device(A, b, c, n, m, B, ragged=ragged)
-        assert full.rc == 0
+    state = sx.BatchState.empty(B, n, m, torch.device("cuda"))
+    entries = {"one shape": lambda **kw: de.batch_device(A, b, c, n, m, B, **kw),
+               "ragged": lambda **kw: de.batch_device(A, b, c, n, m, B, ragged=True, **kw),
+               "state, out NULL": lambda **kw: se.state_call(n, m, B, c, A, b, **kw),
+               "state, out given": lambda **kw: se.state_call(n, m, B, c, A, b, state_out=state, **kw)}
+    for entry, call in entries.items():
+        full = call()
+        assert full.rc == 0, entry
         same_as_refs(de.as_batch_tensors(full), refs, n, m)
         for mask in range(15):  # every combination with at least one NULL
             kw = {name: (ALLOC if mask >> i & 1 else None) for i, name in enumerate(OUTPUTS)}
-            o = de.batch_device(A, b, c, n, m, B, ragged=ragged, **kw)
-            assert o.rc == 0, (ragged, mask)
+            o = call(**kw)
+            assert o.rc == 0, (entry, mask)
             for name in OUTPUTS:
                 assert (getattr(o, name) is None) == (kw[name] is None)
             same_outputs(o, full, ("status", "pivots", "opt", "evicted") + tuple(k for k in OUTPUTS if kw[k] is ALLOC))
