@@ -305,12 +305,51 @@ typedef struct {
     double *T;          /* [count][m][1+n+m]  stored columns b | structural | slack, row-major, dense */
     double *d;          /* [count][1+n+2m]    objective row */
     int *base;          /* [count][m] */
-    int *phase;         /* [count]            1: in phase 1, 2: in phase 2, 0: no state */
+    int *phase;         /* [count]            1: in phase 1, 2: in phase 2, 0: no state (3: see ..._rhs) */
     long long *pivots;  /* [count][2]         pivots done so far in phase 1, phase 2 */
 } simplex_batch_state_t;
 int simplex_solve_batch_device_state(const simplex_batch_device_t *args,
                                      const simplex_batch_state_t *in /* NULL: fresh solve */,
                                      const simplex_batch_state_t *out /* NULL: state not kept */, int recost);
+
+/* ---- device batch state: a new right-hand side (dual simplex) ---- */
+/* Re-solve kept states for a new b, or resume states such a call left.  A state's phase has one more
+ * value here: 3, phase 2's tableau inside the dual loop (dual feasible, primal infeasible), with
+ * phase 2's basis range [0, n+m).  simplex_solve_batch_device_state keeps rejecting 3 with
+ * SIMPLEX_BAD_STATE: a primal resume of a primal-infeasible tableau would be wrong.
+ *
+ * rerhs == 0: a resume.  Phase-1 and phase-2 states behave as in simplex_solve_batch_device_state(args,
+ * in, out, 0), bit for bit; a phase-3 state re-enters the dual loop at pivots[1].  args->A and args->b
+ * are not read and may be NULL.
+ * rerhs != 0: args->A, args->b and args->c are required; b is the new right-hand side and c must be
+ * the costs the state was solved with.  Per problem:
+ *   cold start -- the state is in phase 1, or its objective row is not dual feasible (the eps-argmin of
+ *   d[1 .. 1+n+m) compares below zero: a state that ended UNBOUNDED or was capped in phase 2): the
+ *   problem is built from A, b, c and solved exactly as simplex_solve_batch_device does, every output
+ *   bit for bit, pivots counted from (0, 0);
+ *   warm start -- otherwise.  The kept slack block is S = B^-1 D (D the negation of the rows built with
+ *   b_i < 0, applied to the slack entry too), so T[i][0] = sum_k S[i][k] b[k] and d[0] = sum_i d[1+n+i]
+ *   b[i], each summed in ascending order by fma from +0.0 in 512-element blocks, the block sums added
+ *   left to right; pivots[0] is kept and pivots[1] = 0.  Then the dual loop at width 1+n+m, counting
+ *   into pivots[1]: stop with SIMPLEX_PIVOT_CAP at max_pivots; the leaving row r is the eps-argmin of
+ *   T[i][0]; the loop is left when that minimum does not compare below zero; SIMPLEX_INFEASIBLE when no
+ *   column j has -T[r][j] >= eps; the resident budget (SIMPLEX_NOT_ENDED); the entering variable e is
+ *   the eps-argmin of d[1+j] / -T[r][1+j] over the columns with compare(-T[r][1+j], 0) > 0
+ *   (SIMPLEX_NUMERIC_FAIL if there is none); then the primal loop's update with the pivot T[r][1+e].
+ *   Behind the dual loop phase 2 continues at the same count -- it makes no pivot while the row is
+ *   within eps -- and gives the final status.
+ * What ends inside the dual loop (cap, budget, INFEASIBLE, NUMERIC_FAIL) leaves out->phase 3, anything
+ * later 2.  As in the state entry no outcome has a case of its own: a phase-3 state that ended
+ * INFEASIBLE gives INFEASIBLE again without a pivot, and a capped call resumed with -1 is the uncapped
+ * call bit for bit.  x, opt, objrow and row_width (1+n+m in phases 2 and 3) follow
+ * simplex_solve_batch_device's rules.
+ * Returns simplex_solve_batch_device_state's codes, decided before any device is touched; -2 also for a
+ * NULL in and, with rerhs, a NULL A or b; the strides of A and b are checked only when they are read.
+ * The workspace is simplex_batch_device_workspace(n, m, count); the call only enqueues two small
+ * memsets and one launch on `stream`. */
+int simplex_solve_batch_device_rhs(const simplex_batch_device_t *args, const simplex_batch_state_t *in /* required */,
+                                   const simplex_batch_state_t *out /* NULL: state not kept; may equal in */,
+                                   int rerhs);
 
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through

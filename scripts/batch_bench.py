@@ -10,11 +10,11 @@ same host clock, each call followed by torch.cuda.synchronize(), the three batch
 turns inside every repeat.  The ragged leg (ragged_leg below) then times the ragged device entry
 against the one-shape entry on the same uniform instances, and against solve_batch on problems whose
 dimensions vary inside a 64 x 64 envelope; the state leg (state_leg) what keeping the batch state
-costs and what a warm start from it saves.  The rates are printed and written to
-profiles/batch_bench.txt (or --out).
+costs and what a warm start from it saves; the rhs leg (rhs_leg) what re-solving the kept state for a
+new right-hand side saves.  The rates are printed and written to profiles/batch_bench.txt (or --out).
 
     python scripts/batch_bench.py [--problems 1024] [--subset 64] [--repeats 7]
-                                  [--legs all|uniform|ragged|state] [--out FILE]
+                                  [--legs all|uniform|ragged|state|rhs] [--out FILE]
 """
 import argparse
 import os
@@ -171,6 +171,49 @@ def state_leg(args):
     return lines
 
 
+def rhs_leg(args):
+    """A new right-hand side on the kept state (resume_batch_tensors(state, c, A=, b=)) on the SHAPES'
+    instances: b (1 + 0.1 u), u uniform in [-1, 1], solved warm from the kept optimum (the dual
+    simplex, into a new state, so every repeat starts from the same one) and from scratch, the two
+    calls taking turns inside every repeat, after asserting that both end in the same status on every
+    instance."""
+    ms = lambda t: f"{statistics.median(t) * 1e3:.3f}"  # noqa: E731
+    med = statistics.median
+    lines = ["# rhs: n m problems rerhs_ms rerhs_min_ms rerhs_max_ms scratch_new_b_ms scratch_min_ms scratch_max_ms "
+             "scratch_over_rerhs warm_pivots_mean scratch_pivots_mean"]
+    for n, m in SHAPES:
+        probs = [sx.generateRandomProblem(n, m, 7919 * k + n * 100 + m, 1, 100) for k in range(args.problems)]
+        A, b, c = device_tensors(probs)
+        for p in probs:
+            p.close()
+        u = torch.from_numpy(np.random.default_rng(n * 100 + m).uniform(-1.0, 1.0, size=tuple(b.shape))).cuda()
+        b2 = b * (1.0 + 0.1 * u)
+        kept = sx.solve_batch_tensors(A, b, c, keep_state=True)
+        warm = sx.resume_batch_tensors(kept.state, c, A=A, b=b2, in_place=False)
+        scratch = sx.solve_batch_tensors(A, b2, c)
+        assert kept.evicted == 0 and warm.evicted == 0 and scratch.evicted == 0
+        assert torch.equal(warm.status, scratch.status)
+        piv_warm = float(warm.pivots[:, 1].double().mean())
+        piv_scratch = float(scratch.pivots.sum(dim=1).double().mean())
+
+        def timed(fn):
+            def run():
+                fn()
+                torch.cuda.synchronize()
+            return run
+
+        fns = [timed(lambda: sx.resume_batch_tensors(kept.state, c, A=A, b=b2, in_place=False)),
+               timed(lambda: sx.solve_batch_tensors(A, b2, c))]
+        seconds_in_turn(fns, 2)  # warm-up
+        t_warm, t_new = seconds_in_turn(fns, args.repeats)
+        line = (f"{n} {m} {len(probs)} {ms(t_warm)} {min(t_warm) * 1e3:.3f} {max(t_warm) * 1e3:.3f} {ms(t_new)} "
+                f"{min(t_new) * 1e3:.3f} {max(t_new) * 1e3:.3f} {med(t_new) / med(t_warm):.2f} "
+                f"{piv_warm:.1f} {piv_scratch:.1f}")
+        print(line, flush=True)
+        lines.append(line)
+    return lines
+
+
 def mixed_dims_case(args, dims, n, m):
     """problems of the given (n_k, m_k) in an n x m envelope whose padding is NaN: solve_batch on the
     host problems and the ragged entry in turn; then the ragged entry with its default order (built
@@ -216,7 +259,7 @@ def main():
     ap.add_argument("--problems", type=int, default=1024)
     ap.add_argument("--subset", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--legs", choices=["all", "uniform", "ragged", "state"], default="all")
+    ap.add_argument("--legs", choices=["all", "uniform", "ragged", "state", "rhs"], default="all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.txt"))
     args = ap.parse_args()
 
@@ -262,6 +305,8 @@ def main():
         lines += ragged_leg(args)
     if args.legs in ("all", "state"):
         lines += state_leg(args)
+    if args.legs in ("all", "rhs"):
+        lines += rhs_leg(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")

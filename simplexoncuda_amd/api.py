@@ -224,10 +224,11 @@ class BatchState:
     T: object        # float64 [B, m, 1 + n + m]: the stored columns b | structural | slack
     d: object        # float64 [B, 1 + n + 2m]: the objective row
     base: object     # int32 [B, m]
-    phase: object    # int32 [B]: 1 in phase 1, 2 in phase 2, 0 no state
+    phase: object    # int32 [B]: 1 in phase 1, 2 in phase 2, 0 no state; 3 inside the dual loop (rhs)
     pivots: object   # int64 [B, 2]: pivots done so far in phase 1, phase 2
     n: int
     m: int
+    rhs: bool = False  # written by simplex_solve_batch_device_rhs: a problem may stand in phase 3
 
     @classmethod
     def empty(cls, B, n, m, device):
@@ -429,10 +430,22 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     return out
 
 
-def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=False, finish=True, in_place=True):
+def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=False, finish=True, in_place=True,
+                         A=None, b=None):
     """Continue the problems of a BatchState on the device (simplex_solve_batch_device_state): no A,
     no b, no host copy.  c is [B, n] float64 on the state's device, any strides; it is read when a
     phase-1 state reaches phase 2 and for recost.
+
+    With A [B, m, n] and b [B, m] (both, float64 on the state's device, any strides; not with recost)
+    the kept states are re-solved for the new right-hand side b (simplex_solve_batch_device_rhs); A
+    and c must be what the state was solved with.  A problem whose kept objective row is still dual
+    feasible (it ended FEASIBLE, or stands in the dual loop) is warm-started: the new right-hand-side
+    column and objective are computed from the kept tableau, the dual simplex pivots until the column
+    is primal feasible -- counting into pivots[:, 1] from 0, pivots[:, 0] kept -- and phase 2 finishes.
+    Every other problem (a phase-1 state, one that ended UNBOUNDED or was capped in phase 2) is solved
+    from A, b, c as solve_batch_tensors does.  A problem that the cap or the resident budget stops
+    inside the dual loop, or that the dual loop finds INFEASIBLE, is kept in phase 3; the returned
+    state remembers the entry (BatchState.rhs), and a later plain resume of it continues the dual loop.
 
     A problem in phase 1 continues phase 1 behind its saved pivots and then runs phase 2 with c; one
     in phase 2 continues phase 2, or with recost=True restarts phase 2 from pivot 0 on c from its
@@ -451,6 +464,10 @@ def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=Fa
 
     if not isinstance(state, BatchState):
         raise TypeError(f"resume_batch_tensors: state must be a BatchState, not {type(state).__name__}")
+    if (A is None) != (b is None):
+        raise ValueError("resume_batch_tensors: a new right-hand side needs A and b, both")
+    if A is not None and recost:
+        raise ValueError("resume_batch_tensors: recost is not combined with a new right-hand side (A, b)")
     n, m = state.n, state.m
     B = state.phase.shape[0]
     dev = state.T.device
@@ -468,22 +485,35 @@ def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=Fa
         raise TypeError(f"resume_batch_tensors: c must be float64, not {c.dtype}")
     if tuple(c.shape) != (B, n):
         raise ValueError(f"resume_batch_tensors: c must be [{B}, {n}]; got {tuple(c.shape)}")
+    if A is not None and _check_device_shapes("resume_batch_tensors", A, b, c, batch=True) != (B, m, n):
+        raise ValueError(f"resume_batch_tensors: A must be [{B}, {m}, {n}]; got {tuple(A.shape)}")
     if n < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
         raise ValueError(f"resume_batch_tensors: no resident state exists for {n} variables x {m} constraints")
     if dev.type != "cuda":
         raise ValueError(f"resume_batch_tensors: the state is on {dev}; it must be on a GPU")
     if c.device != dev:
         raise ValueError(f"resume_batch_tensors: c is on {c.device}; it must be on the state's device, {dev}")
+    if A is not None and (A.device != dev or b.device != dev):
+        raise ValueError(f"resume_batch_tensors: A and b must be on the state's device, {dev}")
+    rerhs = A is not None and b is not None
+    # a re-cost is the state entry's; it refuses a problem in phase 3 (BAD_STATE)
+    through_rhs = rerhs or (bool(state.rhs) and not recost)
     new = state
 
     def prepare():
         nonlocal new
         if not in_place:
             new = BatchState.empty(B, n, m, dev)
-        return "simplex_solve_batch_device_state", (ctypes.byref(state._struct()), ctypes.byref(new._struct()),
-                                                    1 if recost else 0)
+        new.rhs = through_rhs
+        pair = (ctypes.byref(state._struct()), ctypes.byref(new._struct()))
+        if through_rhs:
+            return "simplex_solve_batch_device_rhs", pair + (1 if rerhs else 0,)
+        return "simplex_solve_batch_device_state", pair + (1 if recost else 0,)
 
     source = dict(c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
+    if rerhs:
+        source.update(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
+                      b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1))
     outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
     out = BatchTensors(*outputs, None, None, new)
     if finish:

@@ -20,8 +20,10 @@
 // source with A_sr = 1, A_sc = m -- results finished on the host), k_batch_solve_dev
 // (simplex_solve_batch_device: one shape, the caller's strides, every result written by the kernel),
 // k_batch_solve_rag (simplex_solve_batch_device_ragged: the same with per-problem dimensions
-// inside one envelope shape) and k_batch_solve_st (simplex_solve_batch_device_state: k_batch_solve_dev
-// that can load a problem's working set from a saved state and write it to one).
+// inside one envelope shape), k_batch_solve_st (simplex_solve_batch_device_state: k_batch_solve_dev
+// that can load a problem's working set from a saved state and write it to one) and k_batch_solve_rhs
+// (simplex_solve_batch_device_rhs: a saved state re-solved for a new right-hand side by the dual
+// simplex, wg_dual, which shares its pivot, WG_PIVOT, with the primal loop).
 // What surrounds the method is written once where that costs no time: every kernel names its static
 // LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
 // entries end with the same epilogue, wg_write_results, which writes a problem's results into the
@@ -133,6 +135,41 @@ __device__ __forceinline__ void wg_update_objective(const BatchWork &w, int N) {
     __syncthreads();
 }
 
+// orc_apply_update with the basis change, the pivot of the primal loop (wg_solve) and of the dual
+// loop (wg_dual), written once: row r leaves, variable e (stored column ce) enters, colE holds the
+// entering column and d_e is the entering variable's entry of d (N wide).  The pivot-row copy and the
+// row factors -(a_ie / p) first -- T is not written before the barrier -- then the row sweep and d.
+// Ends behind a barrier.  Expanded in both loops, which declare w, m, ld, Ns, art0 and the sweep's
+// lane grouping (WG_ROW_LANES), and not a function: as one, inlined, it leaves wg_solve's
+// instructions in the four earlier kernels other than they were.
+#define WG_ROW_LANES()                                                                               \
+    /* the row update gives each row to 16, 32 or 64 consecutive lanes (a row sweep by consecutive */ \
+    /* lanes is conflict-free at any stride; narrow tableaux keep more rows in flight) */            \
+    const int g = Ns <= 16 ? 4 : Ns <= 32 ? 5 : 6;                                                   \
+    const int G = 1 << g, RP = SX_TILE >> g;                                                         \
+    const int rl = (int)threadIdx.x >> g, cl = (int)threadIdx.x & (G - 1)
+#define WG_PIVOT(N, r, e, ce, d_e)                                                                              \
+    do {                                                                                                        \
+        const double *rowr = w.T + (size_t)r * ld;                                                              \
+        const double p = rowr[ce];                                                                              \
+        for (int j = threadIdx.x; j < Ns; j += SX_TILE) w.prow[j] = rowr[j];                                    \
+        for (int i = threadIdx.x; i < m; i += SX_TILE) w.colE[i] = -w.colE[i] / p;                              \
+        if (threadIdx.x == 0) w.base[r] = e;                                                                    \
+        __syncthreads();                                                                                        \
+        for (int i = rl; i < m; i += RP) {                                                                      \
+            double *row = w.T + (size_t)i * ld;                                                                 \
+            if (i == r) {                                                                                       \
+                for (int j = cl; j < Ns; j += G) row[j] = w.prow[j] / p;                                        \
+            } else {                                                                                            \
+                const double f = w.colE[i];                                                                     \
+                for (int j = cl; j < Ns; j += G) row[j] = fma(f, w.prow[j], row[j]);                            \
+            }                                                                                                   \
+        }                                                                                                       \
+        const double fd = -d_e / p;                                                                             \
+        for (int j = threadIdx.x; j < N; j += SX_TILE) w.d[j] = fma(fd, w.prow[j >= art0 ? j - m : j], w.d[j]); \
+        __syncthreads();                                                                                        \
+    } while (0)
+
 // orc_solve at width N, continued behind k0 pivots of the phase: pivots until the phase ends, the cap
 // on the phase's total is reached (SX_PIVOT_CAP) or one more pivot would exceed the resident budget
 // of this call, `budget` pivots behind k0 (SX_EVICTED).  That test sits behind the stop and unbounded
@@ -141,11 +178,7 @@ __device__ __forceinline__ void wg_update_objective(const BatchWork &w, int N) {
 __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max_pivots, long long budget,
                                         long long k0, long long &pivots, const WgScratch &sc) {
     const int n = w.n, m = w.m, ld = w.ld, Ns = 1 + n + m, art0 = Ns;
-    // the row update gives each row to 16, 32 or 64 consecutive lanes (a row sweep by consecutive
-    // lanes is conflict-free at any stride; narrow tableaux keep more rows in flight)
-    const int g = Ns <= 16 ? 4 : Ns <= 32 ? 5 : 6;
-    const int G = 1 << g, RP = SX_TILE >> g;
-    const int rl = (int)threadIdx.x >> g, cl = (int)threadIdx.x & (G - 1);
+    WG_ROW_LANES();
     long long k = k0;
     for (;;) {
         if (max_pivots >= 0 && k >= max_pivots) {
@@ -188,25 +221,69 @@ __device__ __forceinline__ int wg_solve(const BatchWork &w, int N, long long max
             pivots = k;
             return SX_NUMERIC_FAIL;
         }
-        // pivot row copy and row factors -(a_ie / p); T is not written before the barrier
-        const double *rowr = w.T + (size_t)r * ld;
-        const double p = rowr[ce];
-        for (int j = threadIdx.x; j < Ns; j += SX_TILE) w.prow[j] = rowr[j];
-        for (int i = threadIdx.x; i < m; i += SX_TILE) w.colE[i] = -w.colE[i] / p;
-        if (threadIdx.x == 0) w.base[r] = e;
-        __syncthreads();
-        for (int i = rl; i < m; i += RP) {
-            double *row = w.T + (size_t)i * ld;
-            if (i == r) {
-                for (int j = cl; j < Ns; j += G) row[j] = w.prow[j] / p;
-            } else {
-                const double f = w.colE[i];
-                for (int j = cl; j < Ns; j += G) row[j] = fma(f, w.prow[j], row[j]);
-            }
+        WG_PIVOT(N, r, e, ce, dmin);
+        ++k;
+    }
+}
+
+// The dual simplex on phase 2's tableau (width Ns = 1 + n + m), continued behind k0 pivots: the row of
+// the most negative RHS entry leaves (the reference's eps-argmin tree over T[i][0]), the entering
+// variable is the eps-argmin of d[1 + j] / -T[r][1 + j] over the columns with compare(-T[r][1 + j], 0)
+// > 0, and the pivot is the primal loop's (WG_PIVOT).  The objective row stays dual feasible; the
+// loop is left (SX_FEASIBLE: the tableau is primal feasible, phase 2 follows) when no RHS entry
+// compares below zero.  Ends inside the loop with SX_PIVOT_CAP, SX_INFEASIBLE (a negative RHS entry
+// whose row has no entry <= -eps: the row cannot be satisfied), SX_EVICTED -- wg_solve's place: behind
+// the stop tests, in front of the first write -- or SX_NUMERIC_FAIL.  Uniform over the workgroup.
+__device__ __forceinline__ int wg_dual(const BatchWork &w, long long max_pivots, long long budget, long long k0,
+                                       long long &pivots, const WgScratch &sc) {
+    const int m = w.m, ld = w.ld, Ns = 1 + w.n + m, art0 = Ns;
+    WG_ROW_LANES();
+    long long k = k0;
+    for (;;) {
+        if (max_pivots >= 0 && k >= max_pivots) {
+            pivots = k;
+            return SX_PIVOT_CAP;
         }
-        const double fd = -dmin / p;
-        for (int j = threadIdx.x; j < N; j += SX_TILE) w.d[j] = fma(fd, w.prow[j >= art0 ? j - m : j], w.d[j]);
-        __syncthreads();
+        double bmin;
+        int r;
+        wg_argmin(m, [&](int i) { return w.T[(size_t)i * ld]; }, w.parts, sc, bmin, r);
+        if (!(cmp_eps(bmin, 0.0) < 0)) {
+            pivots = k;
+            return SX_FEASIBLE;
+        }
+        if (r < 0 || r >= m) {  // (a value that compares below zero has an index; the row is indexed with it)
+            pivots = k;
+            return SX_NUMERIC_FAIL;
+        }
+        const double *lrow = w.T + (size_t)r * ld;
+        int any = 0;
+        for (int j = 1 + (int)threadIdx.x; j < Ns; j += SX_TILE) any |= -lrow[j] >= SX_EPS;
+        any = __syncthreads_or(any);
+        if (!any) {
+            pivots = k;
+            return SX_INFEASIBLE;
+        }
+        if (k - k0 >= budget) {
+            pivots = k;
+            return SX_EVICTED;
+        }
+        double rv;
+        int e;
+        wg_argmin(
+            Ns - 1,
+            [&](int idx) {
+                const double a = -lrow[1 + idx];
+                return cmp_eps(a, 0.0) > 0 ? w.d[1 + idx] / a : DBL_MAX;
+            },
+            w.parts, sc, rv, e);
+        if (e < 0 || e >= Ns - 1) {
+            pivots = k;
+            return SX_NUMERIC_FAIL;
+        }
+        const int ce = 1 + e;
+        const double d_e = w.d[ce];
+        for (int i = threadIdx.x; i < m; i += SX_TILE) w.colE[i] = w.T[(size_t)i * ld + ce];
+        WG_PIVOT(Ns, r, e, ce, d_e);
         ++k;
     }
 }
@@ -354,6 +431,48 @@ __device__ __forceinline__ void wg_write_results(const BatchDevArgs &a, const Ba
         if (evicted) atomicAdd(a.evicted, 1);
     }
 }
+
+// A saved state (sx_common.hpp BatchState) of problem k into the working set: the stored columns of T
+// re-packed from the dense stride 1 + n + m to the odd ld by consecutive lanes, and d at full width.
+// The basis is loaded by the kernels, through their range test.  No barrier.  This and WG_STORE_STATE
+// are expanded in k_batch_solve_st and k_batch_solve_rhs, which declare w, k, m, Ns, N1 and cells; as
+// functions they leave k_batch_solve_st's instructions other than they were.
+#define WG_LOAD_STATE(in)                                               \
+    do {                                                                \
+        const double *T_in = (in).T + (size_t)k * (size_t)cells;        \
+        for (int x = threadIdx.x; x < cells; x += SX_TILE) {            \
+            const int i = x / Ns;                                       \
+            w.T[(size_t)i * w.ld + (x - i * Ns)] = T_in[x];             \
+        }                                                               \
+        const double *d_in = (in).d + (size_t)k * (size_t)N1;           \
+        for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = d_in[j]; \
+    } while (0)
+// ... and the working set into a state (nothing when out.T is null) with its phase, `ph`; of a problem
+// that failed its kernel's tests (!good) only phase 0 is written.  What phase 2 leaves behind its row
+// in d is stale phase-1 data and is not kept.
+#define WG_STORE_STATE(out, t, good, ph)                                                                            \
+    do {                                                                                                            \
+        if ((out).T != nullptr) {                                                                                   \
+            if (good) {                                                                                             \
+                double *T_out = (out).T + (size_t)k * (size_t)cells;                                                \
+                for (int x = threadIdx.x; x < cells; x += SX_TILE) {                                                \
+                    const int i = x / Ns;                                                                           \
+                    T_out[x] = w.T[(size_t)i * w.ld + (x - i * Ns)];                                                \
+                }                                                                                                   \
+                double *d_out = (out).d + (size_t)k * (size_t)N1;                                                   \
+                for (int j = threadIdx.x; j < N1; j += SX_TILE) d_out[j] = (t).ph2 && j >= Ns ? 0.0 : w.d[j];       \
+                int *base_out = (out).base + (size_t)k * (size_t)m;                                                 \
+                for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = w.base[i];                             \
+            }                                                                                                       \
+            if (threadIdx.x == 0) {                                                                                 \
+                (out).phase[k] = ph;                                                                                \
+                if (good) {                                                                                         \
+                    (out).pivots[2 * (size_t)k] = (t).p1;                                                           \
+                    (out).pivots[2 * (size_t)k + 1] = (t).p2;                                                       \
+                }                                                                                                   \
+            }                                                                                                       \
+        }                                                                                                           \
+    } while (0)
 
 // simplex_solve_batch: ragged problems packed by the host (A column-major, then b, then c), the RHS
 // column, the basis and a BatchRes per problem written out for the host to finish.
@@ -553,13 +672,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
             }
             if (good) {
                 // consecutive lanes walk the dense rows; the working set's stride is the odd ld
-                const double *T_in = a.in.T + (size_t)k * (size_t)cells;
-                for (int x = threadIdx.x; x < cells; x += SX_TILE) {
-                    const int i = x / Ns;
-                    w.T[(size_t)i * w.ld + (x - i * Ns)] = T_in[x];
-                }
-                const double *d_in = a.in.d + (size_t)k * (size_t)N1;
-                for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = d_in[j];
+                WG_LOAD_STATE(a.in);
                 __syncthreads();
                 t.p1 = q1;
                 t.p2 = q2;
@@ -585,27 +698,123 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
         }
         // a problem whose state failed the tests has every output cleared
         wg_write_results(a, w, t, k, good);
-        // the state: what phase 2 leaves behind its row in d is stale phase-1 data and is not kept
-        if (a.out.T != nullptr) {
-            if (good) {
-                double *T_out = a.out.T + (size_t)k * (size_t)cells;
-                for (int x = threadIdx.x; x < cells; x += SX_TILE) {
-                    const int i = x / Ns;
-                    T_out[x] = w.T[(size_t)i * w.ld + (x - i * Ns)];
-                }
-                double *d_out = a.out.d + (size_t)k * (size_t)N1;
-                for (int j = threadIdx.x; j < N1; j += SX_TILE) d_out[j] = t.ph2 && j >= Ns ? 0.0 : w.d[j];
-                int *base_out = a.out.base + (size_t)k * (size_t)m;
-                for (int i = threadIdx.x; i < m; i += SX_TILE) base_out[i] = w.base[i];
+        WG_STORE_STATE(a.out, t, good, !good ? 0 : t.ph2 ? 2 : 1);
+        __syncthreads();  // the next problem overwrites the working set and sc.k
+    }
+}
+
+// simplex_solve_batch_device_rhs: k_batch_solve_st's resume for a state that may stand inside the dual
+// loop (phase 3: phase 2's tableau, primal infeasible), and with a.rerhs the re-solve of a kept state
+// for the call's right-hand side b'.  wg_build starts from [D b | D A | D] (D = diag(+-1), its negation
+// of a row, applied to the slack entry too) and every pivot is a row operation, so a kept tableau is
+// M [D b | D A | D]: its slack block is S = M D, the RHS column of the same basis on b' is S b' and its
+// objective y b' with y the slack entries of d; d itself does not depend on b.  While d is still dual
+// feasible that is the warm start:
+// the new column and objective in wg_update_objective's order, the dual loop (wg_dual) from pivot 0
+// until the column is primal feasible, then phase 2 at the same count, which makes no pivot unless
+// rounding left an entry of d below -eps.  A phase-1 state, or a row that is not dual feasible (a
+// state that ended UNBOUNDED or was capped in phase 2), is a cold start: the problem is built from A,
+// b', c and solved as k_batch_solve_dev does, at the sites every path shares.  Without a.rerhs A and b
+// are not read; phase-1 and phase-2 states are k_batch_solve_st's resume and a phase-3 state
+// re-enters the dual loop behind its saved pivots.  The state's tests are k_batch_solve_st's with
+// phase 3 (the basis range is phase 2's).  What ends inside the dual loop is saved as phase 3.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    WG_SCRATCH(sc);
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    const BatchWork w = wg_carve(W, n, m);
+    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+    // wg_by_col's rule, decided once: the strides are the launch's
+    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    const bool rerhs = a.rerhs != 0;
+    const int cells = m * Ns;  // (a working set holds them, so they fit an int)
+    for (;;) {
+        const unsigned k = wg_next(a.counter, sc);
+        if (k >= (unsigned)a.count) return;
+        // a plain resume reads only c
+        const SxSource src{rerhs ? a.A + (long long)k * a.A_sb : nullptr, a.A_sr, a.A_sc,
+                           rerhs ? a.b + (long long)k * a.b_sb : nullptr, a.b_si, a.c + (long long)k * a.c_sb, a.c_sj};
+        TwoPhase t{SX_BAD_STATE, false, 0, 0};
+        bool dual = false;  // the problem stands inside the dual loop
+        const int ph = a.in.phase[k];
+        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
+        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
+        if (good) {
+            // the basis indexes d (and, through the alias, T): phase 2 knows no artificial variable
+            const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m) : (unsigned)(n + m);
+            const int *base_in = a.in.base + (size_t)k * (size_t)m;
+            int bad = 0;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                const int bi = base_in[i];
+                w.base[i] = bi;
+                bad |= (unsigned)bi >= lim;
             }
-            if (threadIdx.x == 0) {
-                a.out.phase[k] = !good ? 0 : t.ph2 ? 2 : 1;
-                if (good) {
-                    a.out.pivots[2 * (size_t)k] = t.p1;
-                    a.out.pivots[2 * (size_t)k + 1] = t.p2;
-                }
-            }
+            good = !__syncthreads_or(bad);
         }
+        if (good) {
+            bool cold = rerhs && ph == 1;
+            if (!cold) {
+                // consecutive lanes walk the dense rows; the working set's stride is the odd ld
+                WG_LOAD_STATE(a.in);
+                // the new right-hand side, staged in the pivot-row copy (1 + n + m >= m doubles)
+                if (rerhs)
+                    for (int i = threadIdx.x; i < m; i += SX_TILE) w.prow[i] = src.b[(long long)i * src.b_si];
+                __syncthreads();
+                t.p1 = q1;
+                t.p2 = q2;
+                t.ph2 = ph >= 2;
+                dual = ph == 3;
+                if (rerhs) {
+                    // still dual feasible?  wg_solve's entering selection and stop test
+                    double dmin;
+                    int e;
+                    wg_argmin(Ns - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, sc, dmin, e);
+                    cold = cmp_eps(dmin, 0.0) < 0;
+                }
+            }
+            if (cold) {
+                wg_build(w, src, by_col);
+                wg_update_objective(w, N1);
+                t.p1 = t.p2 = 0;
+                t.ph2 = dual = false;
+            } else if (rerhs) {
+                // T[i][0] = S[i][.] b' and, as row m, d[0] = y b': per element the chain of
+                // wg_update_objective (512-element blocks from +0.0 by fma, added left to right).
+                // Consecutive lanes take consecutive rows: the odd ld keeps the gather conflict-free.
+                for (int i = threadIdx.x; i <= m; i += SX_TILE) {
+                    const double *row = (i < m ? w.T + (size_t)i * w.ld : w.d) + 1 + n;
+                    double s = 0.0;
+                    for (int k0 = 0; k0 < m; k0 += SX_TILE) {
+                        const int k1 = k0 + SX_TILE < m ? k0 + SX_TILE : m;
+                        double p = 0.0;
+                        for (int kk = k0; kk < k1; ++kk) p = fma(row[kk], w.prow[kk], p);
+                        s = k0 == 0 ? p : s + p;
+                    }
+                    (i < m ? w.T[(size_t)i * w.ld] : w.d[0]) = s;
+                }
+                __syncthreads();
+                t.p2 = 0;
+                dual = true;
+            }
+            if (!t.ph2) {
+                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
+                if (t.ph2) {
+                    wg_phase2_costs(w, src);
+                    wg_update_objective(w, Ns);
+                    t.p2 = 0;
+                }
+            }
+            if (t.ph2 && dual) {
+                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
+                dual = t.status != SX_FEASIBLE;
+            }
+            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+        }
+        // a problem whose state failed the tests has every output cleared
+        wg_write_results(a, w, t, k, good);
+        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
         __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
@@ -643,6 +852,7 @@ using HostEntry = Entry<BatchArgs, k_batch_solve<true>, k_batch_solve<false>>;
 using DevEntry = Entry<BatchDevArgs, k_batch_solve_dev<true>, k_batch_solve_dev<false>>;
 using RagEntry = Entry<BatchRagArgs, k_batch_solve_rag<true>, k_batch_solve_rag<false>>;
 using StEntry = Entry<BatchStArgs, k_batch_solve_st<true>, k_batch_solve_st<false>>;
+using RhsEntry = Entry<BatchRhsArgs, k_batch_solve_rhs<true>, k_batch_solve_rhs<false>>;
 
 }  // namespace
 
@@ -651,6 +861,7 @@ int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes) {
     case BatchEntry::Dev: return DevEntry::resident(lds, lds_bytes);
     case BatchEntry::Rag: return RagEntry::resident(lds, lds_bytes);
     case BatchEntry::St: return StEntry::resident(lds, lds_bytes);
+    case BatchEntry::Rhs: return RhsEntry::resident(lds, lds_bytes);
     default: return HostEntry::resident(lds, lds_bytes);
     }
 }
@@ -665,4 +876,7 @@ void sx_launch_batch_solve(bool lds, const BatchRagArgs &a, int grid, size_t lds
 }
 void sx_launch_batch_solve(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     StEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+void sx_launch_batch_solve(bool lds, const BatchRhsArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    RhsEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

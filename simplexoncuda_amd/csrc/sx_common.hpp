@@ -441,7 +441,8 @@ struct BatchRagArgs : BatchDevArgs {
 };
 // The state entry (simplex_solve_batch_device_state): BatchDevArgs plus the saved states it loads
 // and writes.  A state is dense per problem: T [m][1 + n + m] (the stored columns b | structural |
-// slack), d [1 + n + 2m], base [m], phase (1, 2; 0: none) and pivots [2].
+// slack), d [1 + n + 2m], base [m], phase (1, 2; 3 for the right-hand-side entry alone; 0: none) and
+// pivots [2].
 struct BatchState {
     double *T, *d;
     int *base, *phase;
@@ -452,11 +453,18 @@ struct BatchStArgs : BatchDevArgs {
     BatchState out;  // T null: the state is not kept; may equal `in` member for member
     int recost;      // a phase-2 state restarts phase 2 on the call's costs
 };
+// The right-hand-side entry (simplex_solve_batch_device_rhs): the state entry's arguments with `in`
+// required; a state's phase may also be 3, phase 2's tableau inside the dual loop.
+struct BatchRhsArgs : BatchDevArgs {
+    BatchState in;   // required
+    BatchState out;  // T null: the state is not kept; may equal `in` member for member
+    int rerhs;       // b is a new right-hand side for the kept states; 0: a resume, only c is read
+};
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
-// The four entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
-enum class BatchEntry { Host, Dev, Rag, St };
+// The five entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
+enum class BatchEntry { Host, Dev, Rag, St, Rhs };
 // workgroups of that entry's kernel the current device holds at once with this much dynamic LDS
 int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes);
 // one launch of the entry the argument struct belongs to
@@ -464,3 +472,4 @@ void sx_launch_batch_solve(bool lds, const BatchArgs &a, int grid, size_t lds_by
 void sx_launch_batch_solve(bool lds, const BatchDevArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchRagArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchRhsArgs &a, int grid, size_t lds_bytes, hipStream_t s);

@@ -2544,7 +2544,7 @@ long long simplex_batch_device_workspace(int n, int m, int count) {
            (long long)batch_device_grid(n, m, count, cls) * sx_batch_lay(n, m).total * (long long)sizeof(double);
 }
 
-// The body the three entries share.  batch_device_plan decides the return code and, for a call that
+// The body the device batch entries share.  batch_device_plan decides the return code and, for a call that
 // launches, fills the kernel's arguments and the launch's shape; batch_device_enqueue enqueues it.
 struct BatchDevPlan {
     BatchDevArgs a;  // complete: ws and slice stay zero for the LDS class
@@ -2637,6 +2637,21 @@ int simplex_solve_batch_device_state(const simplex_batch_device_t *args, const s
                                 BatchStArgs{p.a, in ? BatchState{in->T, in->d, in->base, in->phase, in->pivots} : none,
                                             out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
                                             recost != 0});
+}
+
+// The right-hand-side entry (k_batch_solve_rhs): the state entry's body with `in` required; A and b
+// are the source only with rerhs, else the call is a resume and reads c alone.
+int simplex_solve_batch_device_rhs(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                   const simplex_batch_state_t *out, int rerhs) {
+    BatchDevPlan p;
+    const int rc = batch_device_plan(args, BatchEntry::Rhs, in != nullptr && state_complete(in) && state_complete(out),
+                                     rerhs == 0, &p);
+    if (rc != 0 || p.grid == 0) return rc;
+    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    return batch_device_enqueue(args, p,
+                                BatchRhsArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
+                                             out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
+                                             rerhs != 0});
 }
 
 // The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
