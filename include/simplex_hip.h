@@ -351,6 +351,39 @@ int simplex_solve_batch_device_rhs(const simplex_batch_device_t *args, const sim
                                    const simplex_batch_state_t *out /* NULL: state not kept; may equal in */,
                                    int rerhs);
 
+/* ---- device batch state: new constraint rows (cuts, branching) ---- */
+/* Grow kept states of shape (n, m0) by `added` = q constraint rows to (n, m = m0 + q) and re-solve them.
+ * args describes the GROWN problem: args->m = m, A [count][m][n], b [count][m], c [count][n] through any
+ * non-zero strides, every output in the grown shape, the workspace simplex_batch_device_workspace(n, m,
+ * count).  Rows 0 .. m0 of A and b, and c, must be what `in` was solved with (the caller's contract).
+ * `in` has the shape (n, m0): T [count][m0][1+n+m0], d [count][1+n+2 m0], base [count][m0]; `out` the
+ * grown one.  Write Ns0 = 1+n+m0 and Ns = 1+n+m.
+ * The kernel tests a state against the in-state's own shape: phase in {1, 2, 3}, both pivot counts >= 0,
+ * base[i] in [0, n+2 m0) in phase 1 and in [0, n+m0) otherwise; a failure gives SIMPLEX_BAD_STATE with
+ * simplex_solve_batch_device_state's cleared outputs and out->phase 0.
+ * A state in phase 2 or 3 is loaded into the grown working set: old row i is T_in[i][0 .. Ns0) followed by
+ * q entries of +0.0; d[0 .. Ns0) is the state's and d[Ns0 .. 1+n+2m) is +0.0; base[0 .. m0) is the state's
+ * and base[m0+t] = n+m0+t.
+ *   cold start -- the state is in phase 1, or the eps-argmin of the grown d[1 .. Ns) compares below zero:
+ *   the problem is built from A, b, c and solved exactly as simplex_solve_batch_device does on the grown
+ *   problem, every output bit for bit, pivots counted from (0, 0);
+ *   warm start -- otherwise.  For each new row t < q the raw row is R[0] = b[m0+t], R[1+j] = A[m0+t][j],
+ *   R[1+n+k] = (k == m0+t) ? 1.0 : +0.0, the multipliers are f_i = base[i] < n ? A[m0+t][base[i]] : +0.0
+ *   for i < m0, and the stored entry T[m0+t][j], j in [0, Ns), starts at R[j] and takes fma(-f_i, T[i][j], .)
+ *   for i = 0, 1, .., m0-1 in that order.  The new rows do not depend on each other, d is unchanged,
+ *   pivots[0] is kept and pivots[1] = 0.  Then simplex_solve_batch_device_rhs's dual loop from 0 at width
+ *   Ns and phase 2 at the same count, with that entry's statuses and its phase-3 rule.  The basic
+ *   columns of a new row come out as the chain computes them; they are not forced to zero.
+ * The grown state is a state of simplex_solve_batch_device_rhs for the shape (n, m): a resume (rerhs == 0)
+ * continues a capped dual loop, and a new right-hand side [m] is valid on it.
+ * Returns simplex_solve_batch_device_rhs's codes, decided before any device is touched; -2 also for a NULL
+ * in, A, b or c and for an out that shares a member pointer with in (the shapes differ, so in place is
+ * impossible); -3 also for added < 1 or added >= m.  The call only enqueues two small memsets and one
+ * launch on `stream`. */
+int simplex_solve_batch_device_rows(const simplex_batch_device_t *args,
+                                    const simplex_batch_state_t *in /* required: shape (n, m - added) */,
+                                    const simplex_batch_state_t *out /* NULL: not kept; shape (n, m) */, int added);
+
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through
  * element strides (a transposed or sliced view is not copied; negative strides are accepted, with

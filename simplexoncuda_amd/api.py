@@ -430,6 +430,30 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     return out
 
 
+def _check_state_and_costs(fn, state, c):
+    """a BatchState's tensors and the costs that go with it, checked on the host: (B, n, m, device)"""
+    import torch
+
+    n, m = state.n, state.m
+    B = state.phase.shape[0]
+    dev = state.T.device
+    want = (("T", (B, m, 1 + n + m), torch.float64), ("d", (B, 1 + n + 2 * m), torch.float64),
+            ("base", (B, m), torch.int32), ("phase", (B,), torch.int32), ("pivots", (B, 2), torch.int64))
+    for name, shape, dtype in want:
+        t = getattr(state, name)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{fn}: state.{name} must be a contiguous {dtype} tensor of shape {shape}")
+        if t.device != dev:
+            raise ValueError(f"{fn}: the state's tensors must be on one device")
+    if not isinstance(c, torch.Tensor):
+        raise TypeError(f"{fn}: c must be a torch.Tensor, not {type(c).__name__}")
+    if c.dtype != torch.float64:
+        raise TypeError(f"{fn}: c must be float64, not {c.dtype}")
+    if tuple(c.shape) != (B, n):
+        raise ValueError(f"{fn}: c must be [{B}, {n}]; got {tuple(c.shape)}")
+    return B, n, m, dev
+
+
 def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=False, finish=True, in_place=True,
                          A=None, b=None):
     """Continue the problems of a BatchState on the device (simplex_solve_batch_device_state): no A,
@@ -468,23 +492,7 @@ def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=Fa
         raise ValueError("resume_batch_tensors: a new right-hand side needs A and b, both")
     if A is not None and recost:
         raise ValueError("resume_batch_tensors: recost is not combined with a new right-hand side (A, b)")
-    n, m = state.n, state.m
-    B = state.phase.shape[0]
-    dev = state.T.device
-    want = (("T", (B, m, 1 + n + m), torch.float64), ("d", (B, 1 + n + 2 * m), torch.float64),
-            ("base", (B, m), torch.int32), ("phase", (B,), torch.int32), ("pivots", (B, 2), torch.int64))
-    for name, shape, dtype in want:
-        t = getattr(state, name)
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"resume_batch_tensors: state.{name} must be a contiguous {dtype} tensor of shape {shape}")
-        if t.device != dev:
-            raise ValueError("resume_batch_tensors: the state's tensors must be on one device")
-    if not isinstance(c, torch.Tensor):
-        raise TypeError(f"resume_batch_tensors: c must be a torch.Tensor, not {type(c).__name__}")
-    if c.dtype != torch.float64:
-        raise TypeError(f"resume_batch_tensors: c must be float64, not {c.dtype}")
-    if tuple(c.shape) != (B, n):
-        raise ValueError(f"resume_batch_tensors: c must be [{B}, {n}]; got {tuple(c.shape)}")
+    B, n, m, dev = _check_state_and_costs("resume_batch_tensors", state, c)
     if A is not None and _check_device_shapes("resume_batch_tensors", A, b, c, batch=True) != (B, m, n):
         raise ValueError(f"resume_batch_tensors: A must be [{B}, {m}, {n}]; got {tuple(A.shape)}")
     if n < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
@@ -514,6 +522,60 @@ def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=Fa
     if rerhs:
         source.update(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
                       b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1))
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
+    out = BatchTensors(*outputs, None, None, new)
+    if finish:
+        out.evicted = _evicted_count(out.evicted, B)
+    return out
+
+
+def add_rows_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, finish=True):
+    """Grow the problems of a BatchState by new constraint rows -- cuts, branches, constraints switched
+    on -- and re-solve them on the device (simplex_solve_batch_device_rows).  A [B, m, n] and b [B, m]
+    describe the grown problems, m > state.m: their first state.m rows, and c [B, n], must be what the
+    state was solved with, and the rows behind them are the new ones.  All three are float64 on the
+    state's device, any strides.
+
+    A problem whose kept objective row is dual feasible (it ended FEASIBLE, or stands in the dual loop)
+    is warm-started: the new rows are reduced against the kept basis on the device, their slacks enter
+    the basis, and the dual simplex pivots from there -- counting into pivots[:, 1] from 0, pivots[:, 0]
+    kept -- before phase 2 finishes.  Every other problem (a phase-1 state, one that ended UNBOUNDED or
+    was capped in phase 2) is solved from A, b, c as solve_batch_tensors does on the grown problem.
+
+    Returns a BatchTensors in the grown shape whose .state is a new BatchState of shape (n, m) with
+    rhs=True: a problem that the cap or the resident budget stops inside the dual loop, or that the
+    dual loop finds INFEASIBLE, is kept in phase 3, a plain resume_batch_tensors continues it, and a
+    new right-hand side [B, m] or further rows can follow.  `state` is left untouched.  A state that
+    fails the kernel's checks against its own shape gives that problem BAD_STATE (see
+    resume_batch_tensors).  finish as there."""
+    import torch
+
+    if not isinstance(state, BatchState):
+        raise TypeError(f"add_rows_batch_tensors: state must be a BatchState, not {type(state).__name__}")
+    B, n, m0, dev = _check_state_and_costs("add_rows_batch_tensors", state, c)
+    m = _check_device_shapes("add_rows_batch_tensors", A, b, c, batch=True)[1]  # (c is [B, n], so A is [B, m, n])
+    if m <= m0:
+        raise ValueError(f"add_rows_batch_tensors: A and b must hold more rows than the state's {m0}; got {m}")
+    if n < 1 or m0 < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+        raise ValueError(f"add_rows_batch_tensors: a problem of {n} variables x {m} constraints is not solved by a "
+                         "resident workgroup")
+    if dev.type != "cuda":
+        raise ValueError(f"add_rows_batch_tensors: the state is on {dev}; it must be on a GPU")
+    if c.device != dev:
+        raise ValueError(f"add_rows_batch_tensors: c is on {c.device}; it must be on the state's device, {dev}")
+    if A.device != dev or b.device != dev:
+        raise ValueError(f"add_rows_batch_tensors: A and b must be on the state's device, {dev}")
+    new = None
+
+    def prepare():
+        nonlocal new
+        new = BatchState.empty(B, n, m, dev)
+        new.rhs = True
+        return "simplex_solve_batch_device_rows", (ctypes.byref(state._struct()), ctypes.byref(new._struct()), m - m0)
+
+    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
+                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
+                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
     outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
     out = BatchTensors(*outputs, None, None, new)
     if finish:

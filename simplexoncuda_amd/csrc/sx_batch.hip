@@ -21,9 +21,10 @@
 // (simplex_solve_batch_device: one shape, the caller's strides, every result written by the kernel),
 // k_batch_solve_rag (simplex_solve_batch_device_ragged: the same with per-problem dimensions
 // inside one envelope shape), k_batch_solve_st (simplex_solve_batch_device_state: k_batch_solve_dev
-// that can load a problem's working set from a saved state and write it to one) and k_batch_solve_rhs
+// that can load a problem's working set from a saved state and write it to one), k_batch_solve_rhs
 // (simplex_solve_batch_device_rhs: a saved state re-solved for a new right-hand side by the dual
-// simplex, wg_dual, which shares its pivot, WG_PIVOT, with the primal loop).
+// simplex, wg_dual, which shares its pivot, WG_PIVOT, with the primal loop) and k_batch_solve_rows
+// (simplex_solve_batch_device_rows: a saved state grown by new constraint rows, then the same dual loop).
 // What surrounds the method is written once where that costs no time: every kernel names its static
 // LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
 // entries end with the same epilogue, wg_write_results, which writes a problem's results into the
@@ -819,6 +820,127 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) 
     }
 }
 
+// simplex_solve_batch_device_rows: a kept state of shape (n, m0) grown by q = a.added constraint rows
+// to the call's shape (n, m = m0 + q) and re-solved: k_batch_solve_rhs with another front.  The grown
+// system is [D' b' | D' A' | D'] with D' = diag(D, I), and a new row minus a combination of old rows is
+// a row operation on it, so the grown tableau is again M' [D' b' | D' A' | D'] with the slack block
+// S' = [[S, 0], [-f^T S, I]]: k_batch_solve_rhs's identities hold on it.
+// Load: the dense in-state is walked at its stride 1 + n + m0 into the grown working set (odd ld of
+// the grown shape), old rows end in q entries of +0.0, d ends in +0.0 from 1 + n + m0 on, and the new
+// rows' slacks are basic.  A phase-1 state, or a row d that is not dual feasible, is a cold start from
+// A, b, c at the sites every path shares.  Warm start, per new row t: the multipliers f_i = the row's
+// entry in the column of old row i's basic variable (+0.0 for a basic slack) are staged in colE, then
+// consecutive lanes take consecutive columns j -- the reads of T[i][j] are row-contiguous -- and
+// T[m0 + t][j] = the raw row's entry, then fma(-f_i, T[i][j], .) for i = 0 .. m0 - 1 in that order.
+// The new rows do not depend on each other, d is unchanged, pivots[0] is kept and pivots[1] = 0; then
+// the dual loop (wg_dual) from 0 and phase 2 at the same count.  Only rows m0 .. m of A and b are read
+// unless the problem is cold.  The state's tests are k_batch_solve_rhs's against the in-state's shape.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    WG_SCRATCH(sc);
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    const int q = a.added, m0 = m - q, Ns0 = Ns - q, N10 = Ns0 + m0;  // the in-state's shape
+    const BatchWork w = wg_carve(W, n, m);
+    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+    // wg_by_col's rule, decided once: the strides are the launch's
+    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    const int cells = m * Ns, cells0 = m0 * Ns0;  // (a working set holds them, so they fit an int)
+    for (;;) {
+        const unsigned k = wg_next(a.counter, sc);
+        if (k >= (unsigned)a.count) return;
+        const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
+                           a.c + (long long)k * a.c_sb, a.c_sj};
+        TwoPhase t{SX_BAD_STATE, false, 0, 0};
+        bool dual = false;  // the problem stands inside the dual loop
+        const int ph = a.in.phase[k];
+        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
+        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
+        if (good) {
+            // the in-state's own range: what is valid only for the grown shape is refused
+            const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m0) : (unsigned)(n + m0);
+            const int *base_in = a.in.base + (size_t)k * (size_t)m0;
+            int bad = 0;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                const int bi = i < m0 ? base_in[i] : n + i;  // a new row's slack is basic
+                w.base[i] = bi;
+                bad |= i < m0 && (unsigned)bi >= lim;
+            }
+            good = !__syncthreads_or(bad);
+        }
+        if (good) {
+            bool cold = ph == 1;
+            if (!cold) {
+                // consecutive lanes walk the dense rows of the in-state; the working set's stride is
+                // the grown shape's odd ld
+                const double *T_in = a.in.T + (size_t)k * (size_t)cells0;
+                for (int x = threadIdx.x; x < cells0; x += SX_TILE) {
+                    const int i = x / Ns0;
+                    w.T[(size_t)i * w.ld + (x - i * Ns0)] = T_in[x];
+                }
+                for (int x = threadIdx.x; x < m0 * q; x += SX_TILE) {
+                    const int i = x / q;
+                    w.T[(size_t)i * w.ld + Ns0 + (x - i * q)] = 0.0;
+                }
+                const double *d_in = a.in.d + (size_t)k * (size_t)N10;
+                for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;
+                __syncthreads();
+                // still dual feasible?  wg_solve's entering selection and stop test, at the grown width
+                double dmin;
+                int e;
+                wg_argmin(Ns - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, sc, dmin, e);
+                cold = cmp_eps(dmin, 0.0) < 0;
+            }
+            if (cold) {
+                wg_build(w, src, by_col);
+                wg_update_objective(w, N1);
+                t.p1 = t.p2 = 0;
+                t.ph2 = dual = false;
+            } else {
+                for (int r = m0; r < m; ++r) {
+                    const double *Ar = src.A + (long long)r * src.A_sr;
+                    // the multipliers of the row, once, in colE (m >= m0 doubles, free by now)
+                    for (int i = threadIdx.x; i < m0; i += SX_TILE) {
+                        const int bi = w.base[i];
+                        w.colE[i] = bi < n ? Ar[(long long)bi * src.A_sc] : 0.0;
+                    }
+                    __syncthreads();
+                    double *row = w.T + (size_t)r * w.ld;
+                    for (int j = threadIdx.x; j < Ns; j += SX_TILE) {
+                        double acc = j == 0   ? src.b[(long long)r * src.b_si]
+                                     : j <= n ? Ar[(long long)(j - 1) * src.A_sc]
+                                              : (j - 1 - n == r ? 1.0 : 0.0);
+                        for (int i = 0; i < m0; ++i) acc = fma(-w.colE[i], w.T[(size_t)i * w.ld + j], acc);
+                        row[j] = acc;
+                    }
+                    __syncthreads();  // colE is rewritten for the next row; T is complete behind the last
+                }
+                t.p1 = q1;
+                t.p2 = 0;
+                t.ph2 = dual = true;
+            }
+            if (!t.ph2) {
+                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
+                if (t.ph2) {
+                    wg_phase2_costs(w, src);
+                    wg_update_objective(w, Ns);
+                    t.p2 = 0;
+                }
+            }
+            if (t.ph2 && dual) {
+                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
+                dual = t.status != SX_FEASIBLE;
+            }
+            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+        }
+        // a problem whose state failed the tests has every output cleared
+        wg_write_results(a, w, t, k, good);
+        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
+        __syncthreads();  // the next problem overwrites the working set and sc.k
+    }
+}
+
 // One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
 template <class Args, void (*KL)(Args), void (*KW)(Args)>
 struct Entry {
@@ -853,6 +975,7 @@ using DevEntry = Entry<BatchDevArgs, k_batch_solve_dev<true>, k_batch_solve_dev<
 using RagEntry = Entry<BatchRagArgs, k_batch_solve_rag<true>, k_batch_solve_rag<false>>;
 using StEntry = Entry<BatchStArgs, k_batch_solve_st<true>, k_batch_solve_st<false>>;
 using RhsEntry = Entry<BatchRhsArgs, k_batch_solve_rhs<true>, k_batch_solve_rhs<false>>;
+using RowsEntry = Entry<BatchRowsArgs, k_batch_solve_rows<true>, k_batch_solve_rows<false>>;
 
 }  // namespace
 
@@ -862,6 +985,7 @@ int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes) {
     case BatchEntry::Rag: return RagEntry::resident(lds, lds_bytes);
     case BatchEntry::St: return StEntry::resident(lds, lds_bytes);
     case BatchEntry::Rhs: return RhsEntry::resident(lds, lds_bytes);
+    case BatchEntry::Rows: return RowsEntry::resident(lds, lds_bytes);
     default: return HostEntry::resident(lds, lds_bytes);
     }
 }
@@ -879,4 +1003,7 @@ void sx_launch_batch_solve(bool lds, const BatchStArgs &a, int grid, size_t lds_
 }
 void sx_launch_batch_solve(bool lds, const BatchRhsArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     RhsEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+void sx_launch_batch_solve(bool lds, const BatchRowsArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    RowsEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }
