@@ -384,6 +384,42 @@ int simplex_solve_batch_device_rows(const simplex_batch_device_t *args,
                                     const simplex_batch_state_t *in /* required: shape (n, m - added) */,
                                     const simplex_batch_state_t *out /* NULL: not kept; shape (n, m) */, int added);
 
+/* ---- device batch state: new variable columns (column generation) ---- */
+/* Grow kept states of shape (n0, m) by `added` = p structural columns to (n = n0 + p, m) and re-solve them.
+ * args describes the GROWN problem: args->n = n, A [count][m][n], b [count][m], c [count][n] through any
+ * non-zero strides, every output in the grown shape, the workspace simplex_batch_device_workspace(n, m,
+ * count).  Columns 0 .. n0 of A and c, and b, must be what `in` was solved with (the caller's contract).
+ * `in` has the shape (n0, m): T [count][m][1+n0+m], d [count][1+n0+2m], base [count][m]; `out` the grown
+ * one.  Write Ns0 = 1+n0+m and Ns = 1+n+m.
+ * The kernel tests a state against the in-state's own shape: phase in {1, 2, 3}, both pivot counts >= 0,
+ * base[i] in [0, n0+2m) in phase 1 and in [0, n0+m) otherwise; a failure gives SIMPLEX_BAD_STATE with
+ * simplex_solve_batch_device_state's cleared outputs and out->phase 0.
+ * A state in phase 2 or 3 is loaded into the grown working set, the structural block growing in the
+ * middle: stored column j < 1+n0 stays at j, slack column 1+n0+k moves to 1+n+k, in T and in d;
+ * d[Ns .. 1+n+2m) is +0.0; a basis entry base[i] >= n0 (a slack) becomes base[i] + p.  Then, for t < p,
+ *   T[i][1+n0+t] = sum_k S[i][k] A[k][n0+t]   and   d[1+n0+t] = (sum_i y_i A[i][n0+t]) - c[n0+t],
+ * S the loaded slack block and y the loaded slack entries of d, each sum as simplex_solve_batch_device_rhs
+ * takes S b': ascending by fma from +0.0 in 512-element blocks, the block sums added left to right; the
+ * subtraction of c is one rounded operation behind the sum.  d[0], the right-hand-side column and the old
+ * columns are unchanged; pivots[0] is kept and pivots[1] = 0.
+ *   a phase-2 state is always warm: the old basis stays primal feasible, so phase 2 runs from count 0
+ *   at width Ns, whatever the state's old status was (a capped or UNBOUNDED state simply continues);
+ *   a phase-3 state is warm while the eps-argmin of the grown d[1 .. Ns) does not compare below zero:
+ *   simplex_solve_batch_device_rhs's dual loop from 0, then phase 2 at the same count, with that
+ *   entry's statuses and its phase-3 rule -- a state that an infeasible row or right-hand side left
+ *   inside the dual loop is rescued by a column with a negative entry in the blocking row;
+ *   cold start -- a phase-1 state, or a phase-3 state whose grown row is not dual feasible: the problem
+ *   is built from A, b, c and solved exactly as simplex_solve_batch_device does on the grown problem,
+ *   every output bit for bit, pivots counted from (0, 0).
+ * The grown state is a state of simplex_solve_batch_device_rhs and of simplex_solve_batch_device_rows for
+ * the shape (n, m): a resume, a new right-hand side, further rows and further columns are valid on it.
+ * Returns simplex_solve_batch_device_rows's codes, decided before any device is touched; -2 also for a
+ * NULL in, A, b or c and for an out that shares a member pointer with in; -3 also for added < 1 or
+ * added >= n.  The call only enqueues two small memsets and one launch on `stream`. */
+int simplex_solve_batch_device_cols(const simplex_batch_device_t *args,
+                                    const simplex_batch_state_t *in /* required: shape (n - added, m) */,
+                                    const simplex_batch_state_t *out /* NULL: not kept; shape (n, m) */, int added);
+
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through
  * element strides (a transposed or sliced view is not copied; negative strides are accepted, with

@@ -11,11 +11,11 @@ turns inside every repeat.  The ragged leg (ragged_leg below) then times the rag
 against the one-shape entry on the same uniform instances, and against solve_batch on problems whose
 dimensions vary inside a 64 x 64 envelope; the state leg (state_leg) what keeping the batch state
 costs and what a warm start from it saves; the rhs leg (rhs_leg) what re-solving the kept state for a
-new right-hand side saves; the rows leg (rows_leg) what adding a cut to the kept state saves.  The
-rates are printed and written to profiles/batch_bench.txt (or --out).
+new right-hand side saves; the rows leg (rows_leg) what adding a cut to the kept state saves; the cols
+leg (cols_leg) what adding a priced-in column to it saves.  The rates are printed and written to profiles/batch_bench.txt (or --out).
 
     python scripts/batch_bench.py [--problems 1024] [--subset 64] [--repeats 7]
-                                  [--legs all|uniform|ragged|state|rhs|rows] [--out FILE]
+                                  [--legs all|uniform|ragged|state|rhs|rows|cols] [--out FILE]
 """
 import argparse
 import os
@@ -261,6 +261,53 @@ def rows_leg(args):
     return lines
 
 
+def cols_leg(args):
+    """A new variable on the kept state (add_cols_batch_tensors): instances of n + 1 variables for the
+    SHAPES' (n, m), the state kept of their first n columns; the last column a gets the cost
+    1.5 y a + 1, y the kept duals (the slack entries of the kept objective row), so it prices in on
+    every instance.  Solved warm from the kept optimum (phase 2 on the grown state) and from scratch
+    on the grown problem, the two calls taking turns inside every repeat, after asserting that both
+    end in the same status on every instance."""
+    ms = lambda t: f"{statistics.median(t) * 1e3:.3f}"  # noqa: E731
+    med = statistics.median
+    lines = ["# cols: n0 m problems add_col_ms add_col_min_ms add_col_max_ms scratch_grown_ms scratch_min_ms scratch_max_ms "
+             "scratch_over_add_col warm_pivots_mean scratch_pivots_mean"]
+    for n, m in SHAPES:
+        probs = [sx.generateRandomProblem(n + 1, m, 7919 * k + (n + 1) * 100 + m, 1, 100) for k in range(args.problems)]
+        A, b, c = device_tensors(probs)
+        for p in probs:
+            p.close()
+        kept = sx.solve_batch_tensors(A[:, :, :n], b, c[:, :n], keep_state=True)
+        assert kept.evicted == 0 and bool((kept.status == sx.FEASIBLE).all())
+        y = kept.state.d[:, 1 + n:1 + n + m]
+        c2 = c.clone()
+        c2[:, n] = 1.5 * (y * A[:, :, n]).sum(dim=1) + 1.0
+        warm = sx.add_cols_batch_tensors(kept.state, A, b, c2)
+        scratch = sx.solve_batch_tensors(A, b, c2)
+        assert warm.evicted == 0 and scratch.evicted == 0
+        assert torch.equal(warm.status, scratch.status)
+        assert bool((warm.pivots[:, 1] >= 1).all())
+        piv_warm = float(warm.pivots[:, 1].double().mean())
+        piv_scratch = float(scratch.pivots.sum(dim=1).double().mean())
+
+        def timed(fn):
+            def run():
+                fn()
+                torch.cuda.synchronize()
+            return run
+
+        fns = [timed(lambda: sx.add_cols_batch_tensors(kept.state, A, b, c2)),
+               timed(lambda: sx.solve_batch_tensors(A, b, c2))]
+        seconds_in_turn(fns, 2)  # warm-up
+        t_warm, t_new = seconds_in_turn(fns, args.repeats)
+        line = (f"{n} {m} {len(probs)} {ms(t_warm)} {min(t_warm) * 1e3:.3f} {max(t_warm) * 1e3:.3f} {ms(t_new)} "
+                f"{min(t_new) * 1e3:.3f} {max(t_new) * 1e3:.3f} {med(t_new) / med(t_warm):.2f} "
+                f"{piv_warm:.1f} {piv_scratch:.1f}")
+        print(line, flush=True)
+        lines.append(line)
+    return lines
+
+
 def mixed_dims_case(args, dims, n, m):
     """problems of the given (n_k, m_k) in an n x m envelope whose padding is NaN: solve_batch on the
     host problems and the ragged entry in turn; then the ragged entry with its default order (built
@@ -306,7 +353,7 @@ def main():
     ap.add_argument("--problems", type=int, default=1024)
     ap.add_argument("--subset", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--legs", choices=["all", "uniform", "ragged", "state", "rhs", "rows"], default="all")
+    ap.add_argument("--legs", choices=["all", "uniform", "ragged", "state", "rhs", "rows", "cols"], default="all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.txt"))
     args = ap.parse_args()
 
@@ -356,6 +403,8 @@ def main():
         lines += rhs_leg(args)
     if args.legs in ("all", "rows"):
         lines += rows_leg(args)
+    if args.legs in ("all", "cols"):
+        lines += cols_leg(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")

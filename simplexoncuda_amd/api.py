@@ -430,8 +430,9 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     return out
 
 
-def _check_state_and_costs(fn, state, c):
-    """a BatchState's tensors and the costs that go with it, checked on the host: (B, n, m, device)"""
+def _check_state_and_costs(fn, state, c, grown=False):
+    """a BatchState's tensors and the costs that go with it, checked on the host: (B, n, m, device).
+    grown: c belongs to a problem of more variables than the state's (the caller tests how many)"""
     import torch
 
     n, m = state.n, state.m
@@ -449,7 +450,10 @@ def _check_state_and_costs(fn, state, c):
         raise TypeError(f"{fn}: c must be a torch.Tensor, not {type(c).__name__}")
     if c.dtype != torch.float64:
         raise TypeError(f"{fn}: c must be float64, not {c.dtype}")
-    if tuple(c.shape) != (B, n):
+    if grown:
+        if c.dim() != 2 or c.shape[0] != B:
+            raise ValueError(f"{fn}: c must be [{B}, n]; got {tuple(c.shape)}")
+    elif tuple(c.shape) != (B, n):
         raise ValueError(f"{fn}: c must be [{B}, {n}]; got {tuple(c.shape)}")
     return B, n, m, dev
 
@@ -572,6 +576,64 @@ def add_rows_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, f
         new = BatchState.empty(B, n, m, dev)
         new.rhs = True
         return "simplex_solve_batch_device_rows", (ctypes.byref(state._struct()), ctypes.byref(new._struct()), m - m0)
+
+    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
+                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
+                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
+    out = BatchTensors(*outputs, None, None, new)
+    if finish:
+        out.evicted = _evicted_count(out.evicted, B)
+    return out
+
+
+def add_cols_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, finish=True):
+    """Grow the problems of a BatchState by new variables -- priced-in columns of a column generation,
+    elastic or penalty variables, actions switched on -- and re-solve them on the device
+    (simplex_solve_batch_device_cols).  A [B, m, n] and c [B, n] describe the grown problems,
+    n > state.n: their first state.n columns, and b [B, m], must be what the state was solved with, and
+    the columns behind them are the new ones.  All three are float64 on the state's device, any strides.
+
+    A problem kept in phase 2 is always warm-started: the new columns are expressed in the kept basis
+    on the device, which stays primal feasible, and phase 2 runs from there -- counting into
+    pivots[:, 1] from 0, pivots[:, 0] kept -- whatever its old status was (a capped or UNBOUNDED
+    problem simply continues).  A problem that stands inside the dual loop (phase 3) re-enters it while
+    its objective row with the new columns is still dual feasible: a column with a negative entry in
+    the blocking row rescues a state that a cut, a branch or a right-hand side left INFEASIBLE.  Every
+    other problem (a phase-1 state, a phase-3 state whose new columns price in) is solved from A, b, c
+    as solve_batch_tensors does on the grown problem.
+
+    Returns a BatchTensors in the grown shape whose .state is a new BatchState of shape (n, m) with
+    rhs=True: a plain resume_batch_tensors, a new right-hand side, add_rows_batch_tensors and further
+    columns can follow.  `state` is left untouched.  A state that fails the kernel's checks against its
+    own shape gives that problem BAD_STATE (see resume_batch_tensors).  finish as there."""
+    import torch
+
+    if not isinstance(state, BatchState):
+        raise TypeError(f"add_cols_batch_tensors: state must be a BatchState, not {type(state).__name__}")
+    B, n0, m, dev = _check_state_and_costs("add_cols_batch_tensors", state, c, grown=True)
+    shape = _check_device_shapes("add_cols_batch_tensors", A, b, c, batch=True)
+    n = shape[2]
+    if n <= n0:
+        raise ValueError(f"add_cols_batch_tensors: A and c must hold more columns than the state's {n0}; got {n}")
+    if shape[:2] != (B, m):
+        raise ValueError(f"add_cols_batch_tensors: A must be [{B}, {m}, n]; got {tuple(A.shape)}")
+    if n0 < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+        raise ValueError(f"add_cols_batch_tensors: a problem of {n} variables x {m} constraints is not solved by a "
+                         "resident workgroup")
+    if dev.type != "cuda":
+        raise ValueError(f"add_cols_batch_tensors: the state is on {dev}; it must be on a GPU")
+    if c.device != dev:
+        raise ValueError(f"add_cols_batch_tensors: c is on {c.device}; it must be on the state's device, {dev}")
+    if A.device != dev or b.device != dev:
+        raise ValueError(f"add_cols_batch_tensors: A and b must be on the state's device, {dev}")
+    new = None
+
+    def prepare():
+        nonlocal new
+        new = BatchState.empty(B, n, m, dev)
+        new.rhs = True
+        return "simplex_solve_batch_device_cols", (ctypes.byref(state._struct()), ctypes.byref(new._struct()), n - n0)
 
     source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
                   b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),

@@ -23,8 +23,10 @@
 // inside one envelope shape), k_batch_solve_st (simplex_solve_batch_device_state: k_batch_solve_dev
 // that can load a problem's working set from a saved state and write it to one), k_batch_solve_rhs
 // (simplex_solve_batch_device_rhs: a saved state re-solved for a new right-hand side by the dual
-// simplex, wg_dual, which shares its pivot, WG_PIVOT, with the primal loop) and k_batch_solve_rows
-// (simplex_solve_batch_device_rows: a saved state grown by new constraint rows, then the same dual loop).
+// simplex, wg_dual, which shares its pivot, WG_PIVOT, with the primal loop), k_batch_solve_rows
+// (simplex_solve_batch_device_rows: a saved state grown by new constraint rows, then the same dual loop)
+// and k_batch_solve_cols (simplex_solve_batch_device_cols: a saved state grown by new structural
+// columns, then phase 2).
 // What surrounds the method is written once where that costs no time: every kernel names its static
 // LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
 // entries end with the same epilogue, wg_write_results, which writes a problem's results into the
@@ -941,6 +943,136 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a
     }
 }
 
+// simplex_solve_batch_device_cols: a kept state of shape (n0, m) grown by p = a.added structural columns
+// to the call's shape (n = n0 + p, m) and re-solved: k_batch_solve_rows with another front.  A kept
+// tableau is M [D b | D A | D] with the slack block S = M D (k_batch_solve_rhs), so the stored form of a
+// new structural column a is M D a = S a and its reduced cost y a - c_new, y the slack entries of d: the
+// re-rhs pass's two sums, once per new column.  S does not change, so the right-hand-side entry's
+// identities hold on the grown state.
+// Load: the dense in-state is walked at its stride 1 + n0 + m into the grown working set (odd ld of the
+// grown shape); the structural block grows in the middle, so stored column j < 1 + n0 stays and the
+// slack column 1 + n0 + k moves to 1 + n + k, in T and in d, d ends in +0.0 from 1 + n + m on, and a
+// basic slack's index moves up by p.  New column t: column n0 + t of A is staged through its strides
+// in the pivot-row copy, then consecutive lanes take consecutive rows (row m is d; the odd ld keeps the
+// gather of S[i][k] conflict-free) and sum in wg_update_objective's order; c is subtracted from row
+// m's sum in one rounded operation.  d[0], the RHS column and the old columns are unchanged, pivots[0]
+// is kept and pivots[1] = 0.  The old basis stays primal feasible, so a phase-2 state is always warm:
+// phase 2 from 0 at the grown width, whatever its old status was.  A phase-3 state re-enters the dual
+// loop (wg_dual) from 0 while the grown d is still dual feasible, then phase 2 at the same count; a
+// phase-1 state, or a phase-3 state whose grown row is not dual feasible, is a cold start from A, b, c
+// at the sites every path shares.  The state's tests are k_batch_solve_rhs's against the in-state's
+// shape.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    WG_SCRATCH(sc);
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    const int p = a.added, n0 = n - p, Ns0 = Ns - p, N10 = Ns0 + m;  // the in-state's shape
+    const BatchWork w = wg_carve(W, n, m);
+    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+    // wg_by_col's rule, decided once: the strides are the launch's
+    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    const int cells = m * Ns, cells0 = m * Ns0;  // (a working set holds them, so they fit an int)
+    for (;;) {
+        const unsigned k = wg_next(a.counter, sc);
+        if (k >= (unsigned)a.count) return;
+        const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
+                           a.c + (long long)k * a.c_sb, a.c_sj};
+        TwoPhase t{SX_BAD_STATE, false, 0, 0};
+        bool dual = false;  // the problem stands inside the dual loop
+        const int ph = a.in.phase[k];
+        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
+        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
+        if (good) {
+            // the in-state's own range: what is valid only for the grown shape is refused
+            const unsigned lim = ph == 1 ? (unsigned)(n0 + 2 * m) : (unsigned)(n0 + m);
+            const int *base_in = a.in.base + (size_t)k * (size_t)m;
+            int bad = 0;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                const int bi = base_in[i];
+                w.base[i] = bi >= n0 ? bi + p : bi;  // a slack moves up with its column
+                bad |= (unsigned)bi >= lim;
+            }
+            good = !__syncthreads_or(bad);
+        }
+        if (good) {
+            bool cold = ph == 1;
+            if (!cold) {
+                // consecutive lanes walk the dense rows of the in-state; the working set's stride is
+                // the grown shape's odd ld, and the slack block lands p columns further on
+                const double *T_in = a.in.T + (size_t)k * (size_t)cells0;
+                for (int x = threadIdx.x; x < cells0; x += SX_TILE) {
+                    const int i = x / Ns0, j = x - i * Ns0;
+                    w.T[(size_t)i * w.ld + (j <= n0 ? j : j + p)] = T_in[x];
+                }
+                const double *d_in = a.in.d + (size_t)k * (size_t)N10;
+                for (int j = threadIdx.x; j < N1; j += SX_TILE)
+                    w.d[j] = j <= n0 ? d_in[j] : j > n && j < Ns ? d_in[j - p] : 0.0;
+                for (int c = 0; c < p; ++c) {
+                    // the new column, staged in the pivot-row copy (1 + n + m >= m doubles)
+                    const double *Ac = src.A + (long long)(n0 + c) * src.A_sc;
+                    for (int i = threadIdx.x; i < m; i += SX_TILE) w.prow[i] = Ac[(long long)i * src.A_sr];
+                    __syncthreads();  // (the first one also completes the load)
+                    // T[i][1 + n0 + c] = S[i][.] a and, as row m, d[1 + n0 + c] = y a - c_new: per element
+                    // the chain of wg_update_objective (512-element blocks from +0.0 by fma, added left
+                    // to right), as k_batch_solve_rhs sums S b'
+                    for (int i = threadIdx.x; i <= m; i += SX_TILE) {
+                        const double *row = (i < m ? w.T + (size_t)i * w.ld : w.d) + 1 + n;
+                        double s = 0.0;
+                        for (int k0 = 0; k0 < m; k0 += SX_TILE) {
+                            const int k1 = k0 + SX_TILE < m ? k0 + SX_TILE : m;
+                            double u = 0.0;
+                            for (int kk = k0; kk < k1; ++kk) u = fma(row[kk], w.prow[kk], u);
+                            s = k0 == 0 ? u : s + u;
+                        }
+                        if (i < m)
+                            w.T[(size_t)i * w.ld + 1 + n0 + c] = s;
+                        else
+                            w.d[1 + n0 + c] = s - src.c[(long long)(n0 + c) * src.c_sj];
+                    }
+                    __syncthreads();  // prow is rewritten for the next column; T and d are complete behind the last
+                }
+                if (ph == 3) {
+                    // still dual feasible?  wg_solve's entering selection and stop test, at the grown width
+                    double dmin;
+                    int e;
+                    wg_argmin(Ns - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, sc, dmin, e);
+                    cold = cmp_eps(dmin, 0.0) < 0;
+                }
+            }
+            if (cold) {
+                wg_build(w, src, by_col);
+                wg_update_objective(w, N1);
+                t.p1 = t.p2 = 0;
+                t.ph2 = dual = false;
+            } else {
+                t.p1 = q1;
+                t.p2 = 0;
+                t.ph2 = true;
+                dual = ph == 3;
+            }
+            if (!t.ph2) {
+                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
+                if (t.ph2) {
+                    wg_phase2_costs(w, src);
+                    wg_update_objective(w, Ns);
+                    t.p2 = 0;
+                }
+            }
+            if (t.ph2 && dual) {
+                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
+                dual = t.status != SX_FEASIBLE;
+            }
+            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+        }
+        // a problem whose state failed the tests has every output cleared
+        wg_write_results(a, w, t, k, good);
+        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
+        __syncthreads();  // the next problem overwrites the working set and sc.k
+    }
+}
+
 // One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
 template <class Args, void (*KL)(Args), void (*KW)(Args)>
 struct Entry {
@@ -976,6 +1108,7 @@ using RagEntry = Entry<BatchRagArgs, k_batch_solve_rag<true>, k_batch_solve_rag<
 using StEntry = Entry<BatchStArgs, k_batch_solve_st<true>, k_batch_solve_st<false>>;
 using RhsEntry = Entry<BatchRhsArgs, k_batch_solve_rhs<true>, k_batch_solve_rhs<false>>;
 using RowsEntry = Entry<BatchRowsArgs, k_batch_solve_rows<true>, k_batch_solve_rows<false>>;
+using ColsEntry = Entry<BatchColsArgs, k_batch_solve_cols<true>, k_batch_solve_cols<false>>;
 
 }  // namespace
 
@@ -986,6 +1119,7 @@ int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes) {
     case BatchEntry::St: return StEntry::resident(lds, lds_bytes);
     case BatchEntry::Rhs: return RhsEntry::resident(lds, lds_bytes);
     case BatchEntry::Rows: return RowsEntry::resident(lds, lds_bytes);
+    case BatchEntry::Cols: return ColsEntry::resident(lds, lds_bytes);
     default: return HostEntry::resident(lds, lds_bytes);
     }
 }
@@ -1006,4 +1140,7 @@ void sx_launch_batch_solve(bool lds, const BatchRhsArgs &a, int grid, size_t lds
 }
 void sx_launch_batch_solve(bool lds, const BatchRowsArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     RowsEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+void sx_launch_batch_solve(bool lds, const BatchColsArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    ColsEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

@@ -467,11 +467,18 @@ struct BatchRowsArgs : BatchDevArgs {
     BatchState out;  // T null: the state is not kept
     int added;       // constraint rows appended behind the in-state's, in [1, m)
 };
+// The columns entry (simplex_solve_batch_device_cols): n and m are the grown shape; `in` has the shape
+// (n - added, m) and `out` the grown one, so the two never coincide.
+struct BatchColsArgs : BatchDevArgs {
+    BatchState in;   // required; dense at the in-state's own strides
+    BatchState out;  // T null: the state is not kept
+    int added;       // structural columns appended behind the in-state's, in [1, n)
+};
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
-// The six entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
-enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows };
+// The seven entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
+enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows, Cols };
 // workgroups of that entry's kernel the current device holds at once with this much dynamic LDS
 int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes);
 // one launch of the entry the argument struct belongs to
@@ -481,3 +488,4 @@ void sx_launch_batch_solve(bool lds, const BatchRagArgs &a, int grid, size_t lds
 void sx_launch_batch_solve(bool lds, const BatchStArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchRhsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchRowsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchColsArgs &a, int grid, size_t lds_bytes, hipStream_t s);

@@ -2673,6 +2673,25 @@ int simplex_solve_batch_device_rows(const simplex_batch_device_t *args, const si
                                               added});
 }
 
+// The columns entry (k_batch_solve_cols): args is the grown problem, `in` the kept state of its first
+// n - added columns.  The shapes differ, so `out` can share no array with `in`.
+int simplex_solve_batch_device_cols(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                    const simplex_batch_state_t *out, int added) {
+    if (args != nullptr && args->count >= 0 && (added < 1 || added >= args->n)) return -3;
+    const bool shared = in != nullptr && out != nullptr &&
+                        (out->T == in->T || out->d == in->d || out->base == in->base || out->phase == in->phase ||
+                         out->pivots == in->pivots);
+    BatchDevPlan p;
+    const int rc = batch_device_plan(args, BatchEntry::Cols,
+                                     in != nullptr && state_complete(in) && state_complete(out) && !shared, false, &p);
+    if (rc != 0 || p.grid == 0) return rc;
+    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    return batch_device_enqueue(args, p,
+                                BatchColsArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
+                                              out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
+                                              added});
+}
+
 // The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
 // The launch is the envelope's: its class, its working set (LDS bytes or slice).  The per-problem
 // dimensions are device data, so the kernel tests them (SX_BAD_SHAPE).
