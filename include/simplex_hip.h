@@ -420,6 +420,50 @@ int simplex_solve_batch_device_cols(const simplex_batch_device_t *args,
                                     const simplex_batch_state_t *in /* required: shape (n - added, m) */,
                                     const simplex_batch_state_t *out /* NULL: not kept; shape (n, m) */, int added);
 
+/* ---- device batch state: rows or columns taken out again (cut purging, undone branches) ---- */
+/* Reduce kept states by `dropped` = q constraint rows (kind 0: shape (n, m + q) to (n, m)) or q structural
+ * columns (kind 1: shape (n + q, m) to (n, m)) and re-solve them.  args describes the REDUCED problem:
+ * A [count][m][n], b [count][m], c [count][n] through any non-zero strides -- what `in` was solved with,
+ * with the named rows or columns deleted (the caller's contract); they are read only when a problem goes
+ * cold -- and every output in the reduced shape.  `in` has the in-state's shape (n_in, m_in), `out` the
+ * reduced one.  idx [count][q], dense int32 on the device, holds problem k's own indices: strictly
+ * ascending, in [0, m_in) or [0, n_in); a list that is not gets what a state that fails its range test
+ * gets: SIMPLEX_BAD_STATE, simplex_solve_batch_device_state's cleared outputs and out->phase 0.
+ * The kernel works in the in-state's shape, so the class (simplex_batch_class) and the workspace
+ * (simplex_batch_device_workspace(n_in, m_in, count)) are that shape's.  A state is tested against its own
+ * shape as simplex_solve_batch_device_rhs tests it, then loaded, and the drops are applied one at a time
+ * in descending index order, each at the shape the earlier ones left:
+ *   row r (slack n + r, stored column 1 + n + r): a basic slack's row and column are deleted without
+ *   arithmetic.  A nonbasic slack is first forced into the basis: with an entry >= eps in its column the
+ *   leaving row is the primal ratio eps-argmin; else with an entry <= -eps the same argmin over the
+ *   negated column (the slack leaves the problem, so it may move down; the pivot element is negative);
+ *   else the problem is cold.  The pivot is the primal loop's; then the slack's row and column go.
+ *   column j: a nonbasic column is deleted without arithmetic.  One that is basic in row i is forced out
+ *   by a dual pivot on that row: with s = +1 if T[i][0] does not compare below zero, else -1, the
+ *   entering variable is the eps-argmin of d[1 + t] / (s T[i][1 + t]) over the other variables t with
+ *   s T[i][1 + t] >= eps; without a candidate the problem is cold.
+ *   Basis entries above a deleted variable go down by one.
+ * Warm or cold: a phase-1 state is cold; a phase-3 state with row drops is warm only if every dropped
+ * slack is basic; column drops of which one is basic are warm only while the eps-argmin of the loaded
+ * d[1 .. 1 + n_in + m_in) does not compare below zero (tested once, before the first drop).  A cold
+ * problem is built from A, b, c and solved exactly as simplex_solve_batch_device does on the reduced
+ * problem, every output bit for bit, pivots counted from (0, 0).
+ * Counts: pivots[0] is kept and pivots[1] starts at f, the number of forced pivots, which belong to the
+ * load: neither max_pivots nor the resident budget counts them.  Behind the drops a phase-3 state, or a
+ * column drop with f > 0, runs simplex_solve_batch_device_rhs's dual loop from f and then phase 2 at the
+ * same count, with that entry's statuses and phase-3 rule; everything else runs phase 2 from f.
+ * The reduced state is a state of every state entry for the shape (n, m).
+ * Returns simplex_solve_batch_device_rows's codes, decided before any device is touched; -2 also for a
+ * NULL in, A, b, c or idx and for an out that shares a member pointer with in; -3 also for kind outside
+ * {0, 1}, dropped < 1, a reduced dimension below 1 and an in-state's shape of class 0.  The call only
+ * enqueues two small memsets and one launch on `stream`. */
+int simplex_solve_batch_device_drop(const simplex_batch_device_t *args,
+                                    const simplex_batch_state_t *in /* required: the in-state's shape */,
+                                    simplex_batch_state_t *out /* NULL: not kept; shape (n, m) */,
+                                    int kind /* 0: constraint rows, 1: structural columns */,
+                                    int dropped /* q >= 1, the same for every problem */,
+                                    const int *idx /* device, int32 [count][dropped], dense */);
+
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through
  * element strides (a transposed or sliced view is not copied; negative strides are accepted, with

@@ -12,10 +12,11 @@ against the one-shape entry on the same uniform instances, and against solve_bat
 dimensions vary inside a 64 x 64 envelope; the state leg (state_leg) what keeping the batch state
 costs and what a warm start from it saves; the rhs leg (rhs_leg) what re-solving the kept state for a
 new right-hand side saves; the rows leg (rows_leg) what adding a cut to the kept state saves; the cols
-leg (cols_leg) what adding a priced-in column to it saves.  The rates are printed and written to profiles/batch_bench.txt (or --out).
+leg (cols_leg) what adding a priced-in column to it saves; the drop leg (drop_leg) what taking that cut or that
+column out of the kept state again saves.  The rates are printed and written to profiles/batch_bench.txt (or --out).
 
     python scripts/batch_bench.py [--problems 1024] [--subset 64] [--repeats 7]
-                                  [--legs all|uniform|ragged|state|rhs|rows|cols] [--out FILE]
+                                  [--legs all|uniform|ragged|state|rhs|rows|cols|drop] [--out FILE]
 """
 import argparse
 import os
@@ -308,6 +309,77 @@ def cols_leg(args):
     return lines
 
 
+def drop_leg(args):
+    """A row or a column taken out of the kept state again (drop_rows_batch_tensors,
+    drop_cols_batch_tensors), three cases on the SHAPES' instances: the rows leg's cut a x <= theta a x*
+    added by add_rows_batch_tensors at theta = 0.5 (binding: its slack is forced into the basis first)
+    and at theta = 1.5 (its slack is basic: no pivot) and dropped from the grown state; the cols leg's
+    priced-in column added by add_cols_batch_tensors and dropped again.  Each against solve_batch_tensors
+    on the reduced problem, the two calls taking turns inside every repeat, after asserting that both end
+    in the same status on every instance."""
+    ms = lambda t: f"{statistics.median(t) * 1e3:.3f}"  # noqa: E731
+    med = statistics.median
+    lines = ["# drop: case n_in m_in problems drop_ms drop_min_ms drop_max_ms scratch_reduced_ms scratch_min_ms "
+             "scratch_max_ms scratch_over_drop warm_pivots_mean scratch_pivots_mean   (warm pivots: forced ones included)"]
+
+    def timed(fn):
+        def run():
+            fn()
+            torch.cuda.synchronize()
+        return run
+
+    def measure(case, grown, fn, small):
+        warm = fn()
+        scratch = sx.solve_batch_tensors(*small)
+        assert warm.evicted == 0 and scratch.evicted == 0
+        assert torch.equal(warm.status, scratch.status)
+        piv_warm = float(warm.pivots[:, 1].double().mean())
+        piv_scratch = float(scratch.pivots.sum(dim=1).double().mean())
+        fns = [timed(fn), timed(lambda: sx.solve_batch_tensors(*small))]
+        seconds_in_turn(fns, 2)  # warm-up
+        t_warm, t_new = seconds_in_turn(fns, args.repeats)
+        line = (f"{case} {grown.n} {grown.m} {small[0].shape[0]} {ms(t_warm)} {min(t_warm) * 1e3:.3f} "
+                f"{max(t_warm) * 1e3:.3f} {ms(t_new)} {min(t_new) * 1e3:.3f} {max(t_new) * 1e3:.3f} "
+                f"{med(t_new) / med(t_warm):.2f} {piv_warm:.1f} {piv_scratch:.1f}")
+        print(line, flush=True)
+        lines.append(line)
+
+    for theta in (0.5, 1.5):
+        for n, m in SHAPES:
+            probs = [sx.generateRandomProblem(n, m, 7919 * k + n * 100 + m, 1, 100) for k in range(args.problems)]
+            A, b, c = device_tensors(probs)
+            for p in probs:
+                p.close()
+            kept = sx.solve_batch_tensors(A, b, c, keep_state=True)
+            assert kept.evicted == 0 and bool((kept.status == sx.FEASIBLE).all())
+            a = A[:, 0, :]
+            beta = theta * (a * kept.solution).sum(dim=1)
+            A2 = torch.cat([A, a[:, None, :]], dim=1).contiguous()
+            b2 = torch.cat([b, beta[:, None]], dim=1).contiguous()
+            grown = sx.add_rows_batch_tensors(kept.state, A2, b2, c)
+            assert grown.evicted == 0
+            rows = torch.full((len(probs), 1), m, dtype=torch.int32, device="cuda")
+            measure(f"row_theta_{theta}", grown.state, lambda: sx.drop_rows_batch_tensors(grown.state, rows, A, b, c),
+                    (A, b, c))
+    for n, m in SHAPES:
+        probs = [sx.generateRandomProblem(n + 1, m, 7919 * k + (n + 1) * 100 + m, 1, 100) for k in range(args.problems)]
+        A, b, c = device_tensors(probs)
+        for p in probs:
+            p.close()
+        A0, c0 = A[:, :, :n].contiguous(), c[:, :n].contiguous()
+        kept = sx.solve_batch_tensors(A0, b, c0, keep_state=True)
+        assert kept.evicted == 0 and bool((kept.status == sx.FEASIBLE).all())
+        y = kept.state.d[:, 1 + n:1 + n + m]
+        c2 = c.clone()
+        c2[:, n] = 1.5 * (y * A[:, :, n]).sum(dim=1) + 1.0
+        grown = sx.add_cols_batch_tensors(kept.state, A, b, c2)
+        assert grown.evicted == 0 and bool((grown.pivots[:, 1] >= 1).all())
+        cols = torch.full((len(probs), 1), n, dtype=torch.int32, device="cuda")
+        measure("priced_in_col", grown.state, lambda: sx.drop_cols_batch_tensors(grown.state, cols, A0, b, c0),
+                (A0, b, c0))
+    return lines
+
+
 def mixed_dims_case(args, dims, n, m):
     """problems of the given (n_k, m_k) in an n x m envelope whose padding is NaN: solve_batch on the
     host problems and the ragged entry in turn; then the ragged entry with its default order (built
@@ -353,7 +425,7 @@ def main():
     ap.add_argument("--problems", type=int, default=1024)
     ap.add_argument("--subset", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--legs", choices=["all", "uniform", "ragged", "state", "rhs", "rows", "cols"], default="all")
+    ap.add_argument("--legs", choices=["all", "uniform", "ragged", "state", "rhs", "rows", "cols", "drop"], default="all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_bench.txt"))
     args = ap.parse_args()
 
@@ -405,6 +477,8 @@ def main():
         lines += rows_leg(args)
     if args.legs in ("all", "cols"):
         lines += cols_leg(args)
+    if args.legs in ("all", "drop"):
+        lines += drop_leg(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -173,6 +173,9 @@ SIGNATURES = {
                                                        ctypes.POINTER(BatchStateT), ctypes.c_int]),
     "simplex_solve_batch_device_cols": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.POINTER(BatchStateT),
                                                        ctypes.POINTER(BatchStateT), ctypes.c_int]),
+    "simplex_solve_batch_device_drop": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.POINTER(BatchStateT),
+                                                       ctypes.POINTER(BatchStateT), ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_void_p]),
     "simplex_solve_device": (ctypes.c_int, [ctypes.POINTER(DeviceSolveT), c_int_p, c_double_p, c_ll_p, c_int_p]),
     "simplex_problem_from_arrays": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "simplex_generate_problem_ex": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,

@@ -308,11 +308,13 @@ def _default_ragged_order(n_active, m_active):
     return torch.argsort(m_k * (1 + n_k + m_k), descending=True, stable=True).to(torch.int32)
 
 
-def _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare):
+def _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare, work_shape=None):
     """What solve_batch_tensors and resume_batch_tensors share, under torch.cuda.device(dev): the
     output tensors, then prepare() -- the caller's own allocations; it returns the C entry's name and
     that entry's arguments behind the BatchDeviceT -- then the workspace and the call itself.
-    source: the BatchDeviceT fields of the problems' data.  Returns BatchTensors' first eight fields."""
+    source: the BatchDeviceT fields of the problems' data.  work_shape: the (n, m) the kernel works in
+    where that is not the problem's own (a drop works in the in-state's); it sizes the workspace.
+    Returns BatchTensors' first eight fields."""
     import torch
 
     lib = _lib.load()
@@ -328,7 +330,7 @@ def _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare):
         evicted = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.int32, device=dev)  # (the call zeroes it)
         entry, extra = prepare()
         if B > 0:
-            ws_bytes = lib.simplex_batch_device_workspace(n, m, B)
+            ws_bytes = lib.simplex_batch_device_workspace(*(work_shape or (n, m)), B)
             if ws_bytes < 0:
                 raise ValueError(f"simplex_batch_device_workspace: bad arguments ({ws_bytes})")
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -432,7 +434,8 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
 
 def _check_state_and_costs(fn, state, c, grown=False):
     """a BatchState's tensors and the costs that go with it, checked on the host: (B, n, m, device).
-    grown: c belongs to a problem of more variables than the state's (the caller tests how many)"""
+    grown: c belongs to a problem of another number of variables than the state's -- more (new columns) or
+    fewer (dropped ones); the caller tests how many"""
     import torch
 
     n, m = state.n, state.m
@@ -643,6 +646,97 @@ def add_cols_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, f
     if finish:
         out.evicted = _evicted_count(out.evicted, B)
     return out
+
+
+def _drop_batch_tensors(fn, kind, state, idx, A, b, c, max_pivots, objective_row, finish):
+    """drop_rows_batch_tensors (kind 0) and drop_cols_batch_tensors (kind 1)"""
+    import torch
+
+    if not isinstance(state, BatchState):
+        raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
+    B, n0, m0, dev = _check_state_and_costs(fn, state, c, grown=True)
+    what = "cols" if kind else "rows"
+    if not isinstance(idx, torch.Tensor):
+        raise TypeError(f"{fn}: {what} must be a torch.Tensor, not {type(idx).__name__}")
+    if idx.dtype != torch.int32:
+        raise TypeError(f"{fn}: {what} must be int32, not {idx.dtype}")
+    if idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] < 1:
+        raise ValueError(f"{fn}: {what} must be [{B}, q] with q >= 1; got {tuple(idx.shape)}")
+    q = idx.shape[1]
+    n, m = (n0 - q, m0) if kind else (n0, m0 - q)
+    if n < 1 or m < 1:
+        raise ValueError(f"{fn}: dropping {q} of the state's {n0 if kind else m0} {what} leaves none")
+    if _check_device_shapes(fn, A, b, c, batch=True) != (B, m, n):
+        raise ValueError(f"{fn}: A must be [{B}, {m}, {n}], the reduced problem; got {tuple(A.shape)}")
+    if n0 < 1 or m0 < 1 or batch_class(n0, m0) == 0:  # (host arithmetic)
+        raise ValueError(f"{fn}: no resident state exists for {n0} variables x {m0} constraints")
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
+    if c.device != dev:
+        raise ValueError(f"{fn}: c is on {c.device}; it must be on the state's device, {dev}")
+    if A.device != dev or b.device != dev:
+        raise ValueError(f"{fn}: A and b must be on the state's device, {dev}")
+    if idx.device != dev:
+        raise ValueError(f"{fn}: {what} is on {idx.device}; it must be on the state's device, {dev}")
+    new = None
+
+    def prepare():
+        nonlocal new, idx
+        idx = idx.contiguous()
+        new = BatchState.empty(B, n, m, dev)
+        new.rhs = True
+        return "simplex_solve_batch_device_drop", (ctypes.byref(state._struct()), ctypes.byref(new._struct()), kind, q,
+                                                   idx.data_ptr())
+
+    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
+                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
+                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare, work_shape=(n0, m0))
+    out = BatchTensors(*outputs, None, None, new)
+    if finish:
+        out.evicted = _evicted_count(out.evicted, B)
+    return out
+
+
+def drop_rows_batch_tensors(state, rows, A, b, c, max_pivots=-1, objective_row=False, finish=True):
+    """Take constraint rows out of the problems of a BatchState -- cuts whose slack went basic, a branch
+    undone, a constraint switched off -- and re-solve them on the device
+    (simplex_solve_batch_device_drop).  rows is int32 [B, q] on the state's device: problem k's own row
+    indices, strictly ascending, in [0, state.m).  A [B, m, n], b [B, m] and c [B, n], m = state.m - q,
+    describe the reduced problems: what the state was solved with, with those rows deleted.  All three
+    are float64 on the state's device, any strides; they are read only for a problem that goes cold.
+
+    A row whose slack is basic (the cut is not binding) leaves without arithmetic.  A binding row's
+    slack is first forced into the basis by one pivot, which pivots[:, 1] counts; phase 2 continues
+    from there, pivots[:, 0] kept.  A problem inside the dual loop (phase 3) stays warm only if every
+    dropped slack is basic -- the impossible cut of an INFEASIBLE state is -- and re-enters that loop.
+    Every other problem (a phase-1 state, a forced pivot without a candidate) is solved from A, b, c as
+    solve_batch_tensors does on the reduced problem.
+
+    Returns a BatchTensors in the reduced shape whose .state is a new BatchState of shape (n, m) with
+    rhs=True: a resume, a new right-hand side, further rows, columns and drops can follow.  `state` is
+    left untouched.  A state that fails the kernel's checks against its own shape, or an index list
+    that is not strictly ascending inside it, gives that problem BAD_STATE (see resume_batch_tensors).
+    finish as there."""
+    return _drop_batch_tensors("drop_rows_batch_tensors", 0, state, rows, A, b, c, max_pivots, objective_row, finish)
+
+
+def drop_cols_batch_tensors(state, cols, A, b, c, max_pivots=-1, objective_row=False, finish=True):
+    """Take variables out of the problems of a BatchState -- generated columns that stayed nonbasic, a
+    variable retired -- and re-solve them on the device (simplex_solve_batch_device_drop).  cols is
+    int32 [B, q] on the state's device: problem k's own column indices, strictly ascending, in
+    [0, state.n).  A [B, m, n], b [B, m] and c [B, n], n = state.n - q, describe the reduced problems:
+    what the state was solved with, with those columns deleted.  All three are float64 on the state's
+    device, any strides; they are read only for a problem that goes cold.
+
+    A nonbasic column leaves without arithmetic.  A basic one is first forced out of the basis by one
+    dual pivot on its row, which pivots[:, 1] counts; the dual simplex and phase 2 continue from there,
+    pivots[:, 0] kept.  That needs a dual feasible objective row: a problem with a basic dropped column
+    whose kept row is not (it ended UNBOUNDED or was capped in phase 2), a phase-1 state and a forced
+    pivot without a candidate are solved from A, b, c as solve_batch_tensors does on the reduced problem.
+
+    Returns and checks as drop_rows_batch_tensors."""
+    return _drop_batch_tensors("drop_cols_batch_tensors", 1, state, cols, A, b, c, max_pivots, objective_row, finish)
 
 
 def _finish_evicted(out, A, b, c, max_pivots):

@@ -24,9 +24,10 @@
 // that can load a problem's working set from a saved state and write it to one), k_batch_solve_rhs
 // (simplex_solve_batch_device_rhs: a saved state re-solved for a new right-hand side by the dual
 // simplex, wg_dual, which shares its pivot, WG_PIVOT, with the primal loop), k_batch_solve_rows
-// (simplex_solve_batch_device_rows: a saved state grown by new constraint rows, then the same dual loop)
-// and k_batch_solve_cols (simplex_solve_batch_device_cols: a saved state grown by new structural
-// columns, then phase 2).
+// (simplex_solve_batch_device_rows: a saved state grown by new constraint rows, then the same dual loop),
+// k_batch_solve_cols (simplex_solve_batch_device_cols: a saved state grown by new structural
+// columns, then phase 2) and k_batch_solve_drop (simplex_solve_batch_device_drop: constraint rows or
+// structural columns taken out of a saved state by forced pivots, then the same loops).
 // What surrounds the method is written once where that costs no time: every kernel names its static
 // LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
 // entries end with the same epilogue, wg_write_results, which writes a problem's results into the
@@ -1073,6 +1074,255 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a
     }
 }
 
+// The tableau of the working set wc with tableau row di (none: di >= wc.m) and stored column dj deleted,
+// moved into wn, the carve of the shape that is left, in the same buffer: T, then d on [0, Ns), then the
+// basis, whose entries above the deleted variable v go down by one.  Everything moves to lower
+// addresses -- every offset of sx_batch_lay grows with the shape, T lies in front of d, d in front of
+// the basis, and the cells are walked in ascending order of both addresses -- so a 512-cell chunk is
+// read into registers, then a barrier, then written: no cell is overwritten before it is read, and what
+// a chunk writes lies below everything a later chunk reads.  Ends behind a barrier.
+__device__ __forceinline__ void wg_shrink(const BatchWork &wc, const BatchWork &wn, int di, int dj, int v) {
+    const int Nsn = 1 + wn.n + wn.m, cells = wn.m * Nsn;
+    for (int x0 = 0; x0 < cells; x0 += SX_TILE) {
+        const int x = x0 + (int)threadIdx.x, i = x / Nsn, j = x - i * Nsn;
+        double val = 0.0;
+        if (x < cells) val = wc.T[(size_t)(i + (i >= di)) * wc.ld + (j + (j >= dj))];
+        __syncthreads();
+        if (x < cells) wn.T[(size_t)i * wn.ld + j] = val;
+    }
+    for (int j0 = 0; j0 < Nsn; j0 += SX_TILE) {
+        const int j = j0 + (int)threadIdx.x;
+        double val = 0.0;
+        if (j < Nsn) val = wc.d[j + (j >= dj)];
+        __syncthreads();
+        if (j < Nsn) wn.d[j] = val;
+    }
+    for (int i0 = 0; i0 < wn.m; i0 += SX_TILE) {
+        const int i = i0 + (int)threadIdx.x;
+        int bi = 0;
+        if (i < wn.m) bi = wc.base[i + (i >= di)];
+        __syncthreads();
+        if (i < wn.m) wn.base[i] = bi - (bi > v);
+    }
+    __syncthreads();
+}
+
+// the tableau row in which variable v is basic, or -1, through the argmin's result slot; uniform over
+// the workgroup.  A basis names a variable once; of a state that names it twice one of the rows is
+// taken.  Ends behind a barrier: the slot is free again.
+__device__ __forceinline__ int wg_basic_row(const BatchWork &w, int v, const WgScratch &sc) {
+    if (threadIdx.x == 0) sc.ri = -1;
+    __syncthreads();
+    for (int i = threadIdx.x; i < w.m; i += SX_TILE)
+        if (w.base[i] == v) sc.ri = i;
+    __syncthreads();
+    const int r = sc.ri;
+    __syncthreads();
+    return r;
+}
+
+// The drops of one problem (k_batch_solve_drop): the q variables ix[0] < .. < ix[q - 1] -- the slacks
+// of constraint rows (kind 0) or structural columns (kind 1) -- leave the tableau loaded at W in the
+// in-state's shape (n, m), last index first, each at the shape the earlier ones left: the tableau is
+// re-carved after every drop (wg_shrink), so the selections see the current shape's positions and
+// lengths and the last carve is the reduced shape's.
+//   a row whose slack is basic, a column that is nonbasic: deleted, no arithmetic;
+//   a row whose slack is nonbasic: the slack is forced in.  It is about to leave the problem, so it may
+//   move in either direction: with an entry >= eps in its column the leaving row is wg_solve's ratio
+//   argmin; else with an entry <= -eps the same argmin on the negated column (the pivot element is then
+//   negative, the other right-hand sides stay non-negative and the row itself is the one deleted);
+//   a basic column: forced out by a dual pivot on its row i, the entering variable the eps-argmin of
+//   d[1 + j] / (s T[i][1 + j]) over the other columns with s T[i][1 + j] >= eps, s the sign that leaves
+//   row i primal feasible.
+// Returns the number of forced pivots (WG_PIVOT, the loops' pivot), or -1 when a forced selection found
+// no candidate: the problem is then solved cold.  Uniform over the workgroup; ends behind a barrier.
+__device__ __forceinline__ int wg_drop(double *W, int n, int m, int kind, int q, const int *ix, const WgScratch &sc) {
+    int forced = 0;
+    for (int t = q - 1; t >= 0; --t) {
+        const BatchWork w = wg_carve(W, n, m);
+        const int ld = w.ld, Ns = 1 + n + m, art0 = Ns;
+        const int v = kind == 0 ? n + ix[t] : ix[t];  // the variable that leaves the problem
+        int r = wg_basic_row(w, v, sc);
+        if ((kind == 0) == (r < 0)) {
+            WG_ROW_LANES();
+            int e;
+            double rv;
+            if (kind == 0) {
+                int pos = 0, neg = 0;
+                for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                    const double a = w.T[(size_t)i * ld + 1 + v];
+                    w.colE[i] = a;
+                    pos |= a >= SX_EPS;
+                    neg |= -a >= SX_EPS;
+                }
+                pos = __syncthreads_or(pos);
+                neg = __syncthreads_or(neg);
+                if (!pos && !neg) return -1;
+                const bool down = !pos;
+                wg_argmin(
+                    m,
+                    [&](int i) {
+                        const double a = down ? -w.colE[i] : w.colE[i], b = w.T[(size_t)i * ld];
+                        return cmp_eps(a, 0.0) > 0 ? b / a : DBL_MAX;
+                    },
+                    w.parts, sc, rv, r);
+                if (r < 0 || r >= m) return -1;
+                e = v;
+            } else {
+                const double *lrow = w.T + (size_t)r * ld;
+                const bool minus = cmp_eps(lrow[0], 0.0) < 0;
+                int any = 0;
+                for (int j = threadIdx.x; j < Ns - 1; j += SX_TILE)
+                    any |= j != v && (minus ? -lrow[1 + j] : lrow[1 + j]) >= SX_EPS;
+                if (!__syncthreads_or(any)) return -1;
+                wg_argmin(
+                    Ns - 1,
+                    [&](int idx) {
+                        const double a = minus ? -lrow[1 + idx] : lrow[1 + idx];
+                        return idx != v && cmp_eps(a, 0.0) > 0 ? w.d[1 + idx] / a : DBL_MAX;
+                    },
+                    w.parts, sc, rv, e);
+                if (e < 0 || e >= Ns - 1) return -1;
+                for (int i = threadIdx.x; i < m; i += SX_TILE) w.colE[i] = w.T[(size_t)i * ld + 1 + e];
+            }
+            const int ce = 1 + e;
+            const double d_e = w.d[ce];
+            WG_PIVOT(Ns, r, e, ce, d_e);
+            ++forced;
+        }
+        if (kind == 0) {
+            wg_shrink(w, wg_carve(W, n, m - 1), r, 1 + v, v);
+            --m;
+        } else {
+            wg_shrink(w, wg_carve(W, n - 1, m), m, 1 + v, v);
+            --n;
+        }
+    }
+    return forced;
+}
+
+// simplex_solve_batch_device_drop: a kept state of shape (n, m + q) (a.kind 0: q = a.dropped constraint
+// rows leave) or (n + q, m) (a.kind 1: structural columns) reduced to the call's shape (n, m) and
+// re-solved: k_batch_solve_cols with another front.  a.kind is a uniform branch, not a template
+// parameter.  The working set -- dynamic LDS or slice -- is the in-state's shape's, because the forced
+// pivots run there; problem k's own indices are a.idx[k][.], strictly ascending and inside the
+// in-state's shape, else the problem gets SX_BAD_STATE as a state that fails its range test does.
+// The in-state is loaded at its own shape and the drops are applied by wg_drop.  Warm or cold: a
+// phase-1 state is cold; a phase-3 state with row drops is warm only if every dropped slack is basic (a
+// forced primal pivot needs a primal feasible column); column drops one of which is basic are warm only
+// while the loaded d is dual feasible (wg_solve's entering selection over d[1 .. Ns_in), once, before
+// the first drop), because the forced dual pivot keeps that; a forced selection without a candidate
+// makes the problem cold.  A cold problem is built from A, b, c of the reduced problem at the sites
+// every path shares.  The forced pivots belong to the load: pivots[0] is kept, pivots[1] starts at
+// their number f, neither the cap nor the budget counts them, and the loops behind start at f: the dual
+// loop (wg_dual) for a phase-3 state and behind a forced dual pivot, then phase 2 at the same count;
+// phase 2 alone otherwise.  A basic slack's column is a unit column and a nonbasic column stands in no
+// identity, so the reduced tableau is M' [D' b' | D' A' | D'] again and k_batch_solve_rhs's identities
+// hold on it.  The state's tests are k_batch_solve_rhs's against the in-state's shape.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
+    WG_SCRATCH(sc);
+    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
+    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    const int kind = a.kind, q = a.dropped;
+    const int n0 = kind == 0 ? n : n + q, m0 = kind == 0 ? m + q : m;  // the in-state's shape
+    const int Ns0 = 1 + n0 + m0, N10 = Ns0 + m0;
+    const BatchWork w = wg_carve(W, n, m), w0 = wg_carve(W, n0, m0);
+    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
+    // wg_by_col's rule, decided once: the strides are the launch's
+    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    const int cells = m * Ns, cells0 = m0 * Ns0;  // (a working set holds them, so they fit an int)
+    for (;;) {
+        const unsigned k = wg_next(a.counter, sc);
+        if (k >= (unsigned)a.count) return;
+        const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
+                           a.c + (long long)k * a.c_sb, a.c_sj};
+        TwoPhase t{SX_BAD_STATE, false, 0, 0};
+        bool dual = false;  // the problem stands inside the dual loop
+        const int ph = a.in.phase[k];
+        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
+        const int *ix = a.idx + (size_t)k * (size_t)q;
+        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
+        if (good) {
+            // the in-state's own range, and the list: strictly ascending inside that shape
+            const unsigned lim = ph == 1 ? (unsigned)(n0 + 2 * m0) : (unsigned)(n0 + m0);
+            const int *base_in = a.in.base + (size_t)k * (size_t)m0;
+            int bad = 0;
+            for (int i = threadIdx.x; i < m0; i += SX_TILE) {
+                const int bi = base_in[i];
+                w0.base[i] = bi;
+                bad |= (unsigned)bi >= lim;
+            }
+            for (int j = threadIdx.x; j < q; j += SX_TILE) {
+                const int v = ix[j];
+                bad |= (unsigned)v >= (unsigned)(kind == 0 ? m0 : n0) || (j > 0 && ix[j - 1] >= v);
+            }
+            good = !__syncthreads_or(bad);
+        }
+        if (good) {
+            bool cold = ph == 1;
+            int forced = 0;
+            if (!cold) {
+                // consecutive lanes walk the dense rows of the in-state at its own shape
+                const double *T_in = a.in.T + (size_t)k * (size_t)cells0;
+                for (int x = threadIdx.x; x < cells0; x += SX_TILE) {
+                    const int i = x / Ns0;
+                    w0.T[(size_t)i * w0.ld + (x - i * Ns0)] = T_in[x];
+                }
+                const double *d_in = a.in.d + (size_t)k * (size_t)N10;
+                for (int j = threadIdx.x; j < N10; j += SX_TILE) w0.d[j] = d_in[j];
+                __syncthreads();
+                if (ph == 3 || kind == 1) {
+                    int basic = 0;  // dropped variables that stand in the basis
+                    for (int j = 0; j < q; ++j) basic += wg_basic_row(w0, kind == 0 ? n0 + ix[j] : ix[j], sc) >= 0;
+                    if (kind == 0) {
+                        cold = basic != q;
+                    } else if (basic > 0) {
+                        // still dual feasible?  wg_solve's entering selection and stop test
+                        double dmin;
+                        int e;
+                        wg_argmin(Ns0 - 1, [&](int idx) { return w0.d[1 + idx]; }, w0.parts, sc, dmin, e);
+                        cold = cmp_eps(dmin, 0.0) < 0;
+                    }
+                }
+                if (!cold) {
+                    forced = wg_drop(W, n0, m0, kind, q, ix, sc);
+                    cold = forced < 0;
+                }
+            }
+            if (cold) {
+                wg_build(w, src, by_col);
+                wg_update_objective(w, N1);
+                t.p1 = t.p2 = 0;
+                t.ph2 = dual = false;
+            } else {
+                t.p1 = q1;
+                t.p2 = forced;
+                t.ph2 = true;
+                dual = ph == 3 || (kind == 1 && forced > 0);
+            }
+            if (!t.ph2) {
+                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
+                if (t.ph2) {
+                    wg_phase2_costs(w, src);
+                    wg_update_objective(w, Ns);
+                    t.p2 = 0;
+                }
+            }
+            if (t.ph2 && dual) {
+                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
+                dual = t.status != SX_FEASIBLE;
+            }
+            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+        }
+        // a problem whose state failed the tests has every output cleared
+        wg_write_results(a, w, t, k, good);
+        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
+        __syncthreads();  // the next problem overwrites the working set and sc.k
+    }
+}
+
 // One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
 template <class Args, void (*KL)(Args), void (*KW)(Args)>
 struct Entry {
@@ -1109,6 +1359,7 @@ using StEntry = Entry<BatchStArgs, k_batch_solve_st<true>, k_batch_solve_st<fals
 using RhsEntry = Entry<BatchRhsArgs, k_batch_solve_rhs<true>, k_batch_solve_rhs<false>>;
 using RowsEntry = Entry<BatchRowsArgs, k_batch_solve_rows<true>, k_batch_solve_rows<false>>;
 using ColsEntry = Entry<BatchColsArgs, k_batch_solve_cols<true>, k_batch_solve_cols<false>>;
+using DropEntry = Entry<BatchDropArgs, k_batch_solve_drop<true>, k_batch_solve_drop<false>>;
 
 }  // namespace
 
@@ -1120,6 +1371,7 @@ int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes) {
     case BatchEntry::Rhs: return RhsEntry::resident(lds, lds_bytes);
     case BatchEntry::Rows: return RowsEntry::resident(lds, lds_bytes);
     case BatchEntry::Cols: return ColsEntry::resident(lds, lds_bytes);
+    case BatchEntry::Drop: return DropEntry::resident(lds, lds_bytes);
     default: return HostEntry::resident(lds, lds_bytes);
     }
 }
@@ -1143,4 +1395,7 @@ void sx_launch_batch_solve(bool lds, const BatchRowsArgs &a, int grid, size_t ld
 }
 void sx_launch_batch_solve(bool lds, const BatchColsArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     ColsEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+void sx_launch_batch_solve(bool lds, const BatchDropArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    DropEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

@@ -474,11 +474,21 @@ struct BatchColsArgs : BatchDevArgs {
     BatchState out;  // T null: the state is not kept
     int added;       // structural columns appended behind the in-state's, in [1, n)
 };
+// The drop entry (simplex_solve_batch_device_drop): n and m are the reduced shape; `in` has the shape
+// (n, m + dropped) (kind 0) or (n + dropped, m) (kind 1) and `out` the reduced one, so the two never
+// coincide.  The working set, ws and slice are the in-state's shape's.
+struct BatchDropArgs : BatchDevArgs {
+    BatchState in;    // required; dense at the in-state's own strides
+    BatchState out;   // T null: the state is not kept
+    int kind;         // 0: constraint rows, 1: structural columns
+    int dropped;      // q >= 1 indices per problem
+    const int *idx;   // [count][dropped] device: strictly ascending, in [0, m + q) or [0, n + q)
+};
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
-// The seven entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
-enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows, Cols };
+// The eight entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
+enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows, Cols, Drop };
 // workgroups of that entry's kernel the current device holds at once with this much dynamic LDS
 int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes);
 // one launch of the entry the argument struct belongs to
@@ -489,3 +499,4 @@ void sx_launch_batch_solve(bool lds, const BatchStArgs &a, int grid, size_t lds_
 void sx_launch_batch_solve(bool lds, const BatchRhsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchRowsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchColsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchDropArgs &a, int grid, size_t lds_bytes, hipStream_t s);

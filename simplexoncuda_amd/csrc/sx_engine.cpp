@@ -2558,13 +2558,16 @@ struct BatchDevPlan {
 // runtime call, in this order: -1, -3, 0 for an empty call, -2, the source's own -2 / -4, -5 for the
 // workspace's address and header.  Then the grid: min(count, the entry's own residency) and, for class
 // 1, no more than the slices simplex_batch_device_workspace(n, m, count) counted, which workspace_bytes
-// must cover (-5).
+// must cover (-5).  wn x wm (the drop entry): the shape the kernel works in -- class, working set, grid and
+// workspace are that shape's -- where it is not the problem's own, which stays the source's and the
+// outputs'.
 static int batch_device_plan(const simplex_batch_device_t *args, BatchEntry entry, bool own_ok, bool c_only,
-                             BatchDevPlan *p) {
+                             BatchDevPlan *p, int wn = 0, int wm = 0) {
     p->grid = 0;
     if (args == nullptr || args->count < 0) return -1;
     const int n = args->n, m = args->m, count = args->count;
-    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(n, m);
+    if (wn < 1 || wm < 1) wn = n, wm = m;
+    const int cls = (n < 1 || m < 1) ? 0 : sx_batch_class(wn, wm);
     if (cls == 0) return -3;
     if (count == 0) return 0;
     if (args->status == nullptr || args->pivots == nullptr || args->opt == nullptr || args->evicted == nullptr || !own_ok)
@@ -2580,12 +2583,12 @@ static int batch_device_plan(const simplex_batch_device_t *args, BatchEntry entr
     if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0 ||
         args->workspace_bytes < SX_BATCH_DEV_HEADER)
         return -5;
-    const long long set = sx_batch_lay(n, m).total;
+    const long long set = sx_batch_lay(wn, wm).total;
     p->lds = cls == 2;
     p->set_bytes = (size_t)set * sizeof(double);
     int grid = std::min(count, sx_batch_resident(entry, p->lds, p->set_bytes));
     if (cls == 1) {
-        const int slices = batch_device_grid(n, m, count, cls);  // what the workspace query counted
+        const int slices = batch_device_grid(wn, wm, count, cls);  // what the workspace query counted
         if (args->workspace_bytes < SX_BATCH_DEV_HEADER + (long long)slices * set * (long long)sizeof(double)) return -5;
         grid = std::min(grid, slices);
     }
@@ -2690,6 +2693,33 @@ int simplex_solve_batch_device_cols(const simplex_batch_device_t *args, const si
                                 BatchColsArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
                                               out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
                                               added});
+}
+
+// The drop entry (k_batch_solve_drop): args is the reduced problem, `in` the kept state of the problem
+// with `dropped` more rows (kind 0) or columns (kind 1).  The kernel works in the in-state's shape.
+int simplex_solve_batch_device_drop(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                    simplex_batch_state_t *out, int kind, int dropped, const int *idx) {
+    int n0 = 0, m0 = 0;
+    if (args != nullptr && args->count >= 0) {
+        if ((kind != 0 && kind != 1) || dropped < 1 || args->n < 1 || args->m < 1) return -3;
+        const long long grown = (long long)(kind == 0 ? args->m : args->n) + dropped;
+        if (grown > 0x7fffffffLL) return -3;
+        n0 = kind == 0 ? args->n : (int)grown;
+        m0 = kind == 0 ? (int)grown : args->m;
+    }
+    const bool shared = in != nullptr && out != nullptr &&
+                        (out->T == in->T || out->d == in->d || out->base == in->base || out->phase == in->phase ||
+                         out->pivots == in->pivots);
+    BatchDevPlan p;
+    const int rc = batch_device_plan(args, BatchEntry::Drop,
+                                     in != nullptr && idx != nullptr && state_complete(in) && state_complete(out) && !shared,
+                                     false, &p, n0, m0);
+    if (rc != 0 || p.grid == 0) return rc;
+    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    return batch_device_enqueue(args, p,
+                                BatchDropArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
+                                              out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
+                                              kind, dropped, idx});
 }
 
 // The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
