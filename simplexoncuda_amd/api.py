@@ -347,6 +347,15 @@ def _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare, 
     return status, pivots, opt, x, base, row, width, evicted
 
 
+def _source_fields(A, b, c):
+    """the BatchDeviceT fields of the problems' data; A and b None: a call that reads c alone"""
+    source = dict(c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
+    if A is not None:
+        source.update(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
+                      b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1))
+    return source
+
+
 def _evicted_count(evicted, B):
     """the launch's evicted count on the host: one 4-byte copy, which waits for the stream"""
     return int(evicted.item()) if B > 0 else 0
@@ -418,10 +427,7 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
             return "simplex_solve_batch_device_state", (None, ctypes.byref(state._struct()), 0)
         return "simplex_solve_batch_device", ()
 
-    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
-                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
-                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
-    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare)
     out = BatchTensors(*outputs, n_active if ragged else None, m_active if ragged else None, state)
     if not finish:
         return out
@@ -525,11 +531,7 @@ def resume_batch_tensors(state, c, max_pivots=-1, objective_row=False, recost=Fa
             return "simplex_solve_batch_device_rhs", pair + (1 if rerhs else 0,)
         return "simplex_solve_batch_device_state", pair + (1 if recost else 0,)
 
-    source = dict(c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
-    if rerhs:
-        source.update(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
-                      b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1))
-    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare)
     out = BatchTensors(*outputs, None, None, new)
     if finish:
         out.evicted = _evicted_count(out.evicted, B)
@@ -555,39 +557,17 @@ def add_rows_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, f
     new right-hand side [B, m] or further rows can follow.  `state` is left untouched.  A state that
     fails the kernel's checks against its own shape gives that problem BAD_STATE (see
     resume_batch_tensors).  finish as there."""
-    import torch
+    def shapes(B, n, m0):
+        m = _check_device_shapes("add_rows_batch_tensors", A, b, c, batch=True)[1]  # (c is [B, n], so A is [B, m, n])
+        if m <= m0:
+            raise ValueError(f"add_rows_batch_tensors: A and b must hold more rows than the state's {m0}; got {m}")
+        if n < 1 or m0 < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+            raise ValueError(f"add_rows_batch_tensors: a problem of {n} variables x {m} constraints is not solved by "
+                             "a resident workgroup")
+        return n, m, (m - m0,), None
 
-    if not isinstance(state, BatchState):
-        raise TypeError(f"add_rows_batch_tensors: state must be a BatchState, not {type(state).__name__}")
-    B, n, m0, dev = _check_state_and_costs("add_rows_batch_tensors", state, c)
-    m = _check_device_shapes("add_rows_batch_tensors", A, b, c, batch=True)[1]  # (c is [B, n], so A is [B, m, n])
-    if m <= m0:
-        raise ValueError(f"add_rows_batch_tensors: A and b must hold more rows than the state's {m0}; got {m}")
-    if n < 1 or m0 < 1 or batch_class(n, m) == 0:  # (host arithmetic)
-        raise ValueError(f"add_rows_batch_tensors: a problem of {n} variables x {m} constraints is not solved by a "
-                         "resident workgroup")
-    if dev.type != "cuda":
-        raise ValueError(f"add_rows_batch_tensors: the state is on {dev}; it must be on a GPU")
-    if c.device != dev:
-        raise ValueError(f"add_rows_batch_tensors: c is on {c.device}; it must be on the state's device, {dev}")
-    if A.device != dev or b.device != dev:
-        raise ValueError(f"add_rows_batch_tensors: A and b must be on the state's device, {dev}")
-    new = None
-
-    def prepare():
-        nonlocal new
-        new = BatchState.empty(B, n, m, dev)
-        new.rhs = True
-        return "simplex_solve_batch_device_rows", (ctypes.byref(state._struct()), ctypes.byref(new._struct()), m - m0)
-
-    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
-                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
-                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
-    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
-    out = BatchTensors(*outputs, None, None, new)
-    if finish:
-        out.evicted = _evicted_count(out.evicted, B)
-    return out
+    return _edit_batch_state("add_rows_batch_tensors", "simplex_solve_batch_device_rows", state, A, b, c, False, shapes,
+                             max_pivots, objective_row, finish)
 
 
 def add_cols_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, finish=True):
@@ -610,38 +590,53 @@ def add_cols_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, f
     rhs=True: a plain resume_batch_tensors, a new right-hand side, add_rows_batch_tensors and further
     columns can follow.  `state` is left untouched.  A state that fails the kernel's checks against its
     own shape gives that problem BAD_STATE (see resume_batch_tensors).  finish as there."""
-    import torch
+    def shapes(B, n0, m):
+        shape = _check_device_shapes("add_cols_batch_tensors", A, b, c, batch=True)
+        n = shape[2]
+        if n <= n0:
+            raise ValueError(f"add_cols_batch_tensors: A and c must hold more columns than the state's {n0}; got {n}")
+        if shape[:2] != (B, m):
+            raise ValueError(f"add_cols_batch_tensors: A must be [{B}, {m}, n]; got {tuple(A.shape)}")
+        if n0 < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+            raise ValueError(f"add_cols_batch_tensors: a problem of {n} variables x {m} constraints is not solved by "
+                             "a resident workgroup")
+        return n, m, (n - n0,), None
 
+    return _edit_batch_state("add_cols_batch_tensors", "simplex_solve_batch_device_cols", state, A, b, c, True, shapes,
+                             max_pivots, objective_row, finish)
+
+
+def _edit_batch_state(fn, entry, state, A, b, c, grown, shapes, max_pivots, objective_row, finish, idx=None, what=None):
+    """What add_rows_, add_cols_ and the drop_*_batch_tensors share: a kept state edited into a new one of
+    another shape (simplex_solve_batch_device_rows, _cols, _drop).  shapes(B, n0, m0), called with the
+    state's checked shape, is the caller's own shape arithmetic with its errors: it returns the call's n
+    and m, the entry's arguments behind the two states, and the shape the kernel works in where that is
+    not (n, m).  idx: the drop entry's index tensor, `what` in messages; it is the entry's last argument."""
     if not isinstance(state, BatchState):
-        raise TypeError(f"add_cols_batch_tensors: state must be a BatchState, not {type(state).__name__}")
-    B, n0, m, dev = _check_state_and_costs("add_cols_batch_tensors", state, c, grown=True)
-    shape = _check_device_shapes("add_cols_batch_tensors", A, b, c, batch=True)
-    n = shape[2]
-    if n <= n0:
-        raise ValueError(f"add_cols_batch_tensors: A and c must hold more columns than the state's {n0}; got {n}")
-    if shape[:2] != (B, m):
-        raise ValueError(f"add_cols_batch_tensors: A must be [{B}, {m}, n]; got {tuple(A.shape)}")
-    if n0 < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
-        raise ValueError(f"add_cols_batch_tensors: a problem of {n} variables x {m} constraints is not solved by a "
-                         "resident workgroup")
+        raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
+    B, n0, m0, dev = _check_state_and_costs(fn, state, c, grown=grown)
+    n, m, tail, work_shape = shapes(B, n0, m0)
     if dev.type != "cuda":
-        raise ValueError(f"add_cols_batch_tensors: the state is on {dev}; it must be on a GPU")
+        raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
     if c.device != dev:
-        raise ValueError(f"add_cols_batch_tensors: c is on {c.device}; it must be on the state's device, {dev}")
+        raise ValueError(f"{fn}: c is on {c.device}; it must be on the state's device, {dev}")
     if A.device != dev or b.device != dev:
-        raise ValueError(f"add_cols_batch_tensors: A and b must be on the state's device, {dev}")
+        raise ValueError(f"{fn}: A and b must be on the state's device, {dev}")
+    if idx is not None and idx.device != dev:
+        raise ValueError(f"{fn}: {what} is on {idx.device}; it must be on the state's device, {dev}")
     new = None
 
     def prepare():
-        nonlocal new
+        nonlocal new, idx
+        if idx is not None:
+            idx = idx.contiguous()
         new = BatchState.empty(B, n, m, dev)
         new.rhs = True
-        return "simplex_solve_batch_device_cols", (ctypes.byref(state._struct()), ctypes.byref(new._struct()), n - n0)
+        return entry, (ctypes.byref(state._struct()), ctypes.byref(new._struct())) + tail + (
+            () if idx is None else (idx.data_ptr(),))
 
-    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
-                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
-                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
-    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare)
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare,
+                                work_shape=work_shape)
     out = BatchTensors(*outputs, None, None, new)
     if finish:
         out.evicted = _evicted_count(out.evicted, B)
@@ -650,52 +645,29 @@ def add_cols_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, f
 
 def _drop_batch_tensors(fn, kind, state, idx, A, b, c, max_pivots, objective_row, finish):
     """drop_rows_batch_tensors (kind 0) and drop_cols_batch_tensors (kind 1)"""
-    import torch
-
-    if not isinstance(state, BatchState):
-        raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
-    B, n0, m0, dev = _check_state_and_costs(fn, state, c, grown=True)
     what = "cols" if kind else "rows"
-    if not isinstance(idx, torch.Tensor):
-        raise TypeError(f"{fn}: {what} must be a torch.Tensor, not {type(idx).__name__}")
-    if idx.dtype != torch.int32:
-        raise TypeError(f"{fn}: {what} must be int32, not {idx.dtype}")
-    if idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] < 1:
-        raise ValueError(f"{fn}: {what} must be [{B}, q] with q >= 1; got {tuple(idx.shape)}")
-    q = idx.shape[1]
-    n, m = (n0 - q, m0) if kind else (n0, m0 - q)
-    if n < 1 or m < 1:
-        raise ValueError(f"{fn}: dropping {q} of the state's {n0 if kind else m0} {what} leaves none")
-    if _check_device_shapes(fn, A, b, c, batch=True) != (B, m, n):
-        raise ValueError(f"{fn}: A must be [{B}, {m}, {n}], the reduced problem; got {tuple(A.shape)}")
-    if n0 < 1 or m0 < 1 or batch_class(n0, m0) == 0:  # (host arithmetic)
-        raise ValueError(f"{fn}: no resident state exists for {n0} variables x {m0} constraints")
-    if dev.type != "cuda":
-        raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
-    if c.device != dev:
-        raise ValueError(f"{fn}: c is on {c.device}; it must be on the state's device, {dev}")
-    if A.device != dev or b.device != dev:
-        raise ValueError(f"{fn}: A and b must be on the state's device, {dev}")
-    if idx.device != dev:
-        raise ValueError(f"{fn}: {what} is on {idx.device}; it must be on the state's device, {dev}")
-    new = None
 
-    def prepare():
-        nonlocal new, idx
-        idx = idx.contiguous()
-        new = BatchState.empty(B, n, m, dev)
-        new.rhs = True
-        return "simplex_solve_batch_device_drop", (ctypes.byref(state._struct()), ctypes.byref(new._struct()), kind, q,
-                                                   idx.data_ptr())
+    def shapes(B, n0, m0):
+        import torch
 
-    source = dict(A=A.data_ptr(), A_sb=A.stride(0), A_sr=A.stride(1), A_sc=A.stride(2),
-                  b=b.data_ptr(), b_sb=b.stride(0), b_si=b.stride(1),
-                  c=c.data_ptr(), c_sb=c.stride(0), c_sj=c.stride(1))
-    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, source, prepare, work_shape=(n0, m0))
-    out = BatchTensors(*outputs, None, None, new)
-    if finish:
-        out.evicted = _evicted_count(out.evicted, B)
-    return out
+        if not isinstance(idx, torch.Tensor):
+            raise TypeError(f"{fn}: {what} must be a torch.Tensor, not {type(idx).__name__}")
+        if idx.dtype != torch.int32:
+            raise TypeError(f"{fn}: {what} must be int32, not {idx.dtype}")
+        if idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] < 1:
+            raise ValueError(f"{fn}: {what} must be [{B}, q] with q >= 1; got {tuple(idx.shape)}")
+        q = idx.shape[1]
+        n, m = (n0 - q, m0) if kind else (n0, m0 - q)
+        if n < 1 or m < 1:
+            raise ValueError(f"{fn}: dropping {q} of the state's {n0 if kind else m0} {what} leaves none")
+        if _check_device_shapes(fn, A, b, c, batch=True) != (B, m, n):
+            raise ValueError(f"{fn}: A must be [{B}, {m}, {n}], the reduced problem; got {tuple(A.shape)}")
+        if n0 < 1 or m0 < 1 or batch_class(n0, m0) == 0:  # (host arithmetic)
+            raise ValueError(f"{fn}: no resident state exists for {n0} variables x {m0} constraints")
+        return n, m, (kind, q), (n0, m0)
+
+    return _edit_batch_state(fn, "simplex_solve_batch_device_drop", state, A, b, c, True, shapes, max_pivots,
+                             objective_row, finish, idx=idx, what=what)
 
 
 def drop_rows_batch_tensors(state, rows, A, b, c, max_pivots=-1, objective_row=False, finish=True):

@@ -31,7 +31,9 @@
 // What surrounds the method is written once where that costs no time: every kernel names its static
 // LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
 // entries end with the same epilogue, wg_write_results, which writes a problem's results into the
-// caller's dense arrays; k_batch_solve_rag keeps that epilogue written out over its envelope.
+// caller's dense arrays; k_batch_solve_rag keeps that epilogue written out over its envelope.  The five
+// kernels on a saved state share their head, the state's tests, the cold start, the loops behind the
+// front and the end (WG_KEPT_HEAD .. WG_KEPT_END), so each shows only its own front.
 
 #include <float.h>
 
@@ -436,19 +438,25 @@ __device__ __forceinline__ void wg_write_results(const BatchDevArgs &a, const Ba
     }
 }
 
-// A saved state (sx_common.hpp BatchState) of problem k into the working set: the stored columns of T
-// re-packed from the dense stride 1 + n + m to the odd ld by consecutive lanes, and d at full width.
-// The basis is loaded by the kernels, through their range test.  No barrier.  This and WG_STORE_STATE
-// are expanded in k_batch_solve_st and k_batch_solve_rhs, which declare w, k, m, Ns, N1 and cells; as
-// functions they leave k_batch_solve_st's instructions other than they were.
-#define WG_LOAD_STATE(in)                                               \
-    do {                                                                \
-        const double *T_in = (in).T + (size_t)k * (size_t)cells;        \
-        for (int x = threadIdx.x; x < cells; x += SX_TILE) {            \
-            const int i = x / Ns;                                       \
-            w.T[(size_t)i * w.ld + (x - i * Ns)] = T_in[x];             \
-        }                                                               \
-        const double *d_in = (in).d + (size_t)k * (size_t)N1;           \
+// The stored columns of a saved tableau, dense at T_in with stride Ns0 (cells0 of them), into the
+// working set wk, whose shape may be another: re-packed to wk's odd ld by consecutive lanes, which walk
+// the dense rows.  No barrier.
+__device__ __forceinline__ void wg_load_T(const BatchWork &wk, const double *T_in, int Ns0, int cells0) {
+    for (int x = threadIdx.x; x < cells0; x += SX_TILE) {
+        const int i = x / Ns0;
+        wk.T[(size_t)i * wk.ld + (x - i * Ns0)] = T_in[x];
+    }
+}
+
+// A saved state (sx_common.hpp BatchState) of problem k into the working set of the same shape: the
+// stored columns of T (wg_load_T) and d at full width.  The basis is loaded by the kernels, through
+// their range test (WG_STATE_TEST).  No barrier.  This and WG_STORE_STATE are expanded in the
+// kept-state kernels, which declare w, k, m, Ns, N1 and cells; as functions they leave
+// k_batch_solve_st's instructions other than they were.
+#define WG_LOAD_STATE(in)                                                 \
+    do {                                                                  \
+        wg_load_T(w, (in).T + (size_t)k * (size_t)cells, Ns, cells);      \
+        const double *d_in = (in).d + (size_t)k * (size_t)N1;             \
         for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = d_in[j]; \
     } while (0)
 // ... and the working set into a state (nothing when out.T is null) with its phase, `ph`; of a problem
@@ -476,6 +484,117 @@ __device__ __forceinline__ void wg_write_results(const BatchDevArgs &a, const Ba
                 }                                                                                                   \
             }                                                                                                       \
         }                                                                                                           \
+    } while (0)
+
+// What the kernels on a kept state share (k_batch_solve_st, _rhs, _rows, _cols, _drop), written once;
+// each kernel keeps its own front: how the in-state is embedded into the working set and what makes the
+// tableau canonical again.  All but the dense load (wg_load_T) are macros, expanded in the kernel's
+// body, which declares a, sc, w, src, k and the names of the head: as functions, and even with the
+// head's declarations in another order, they leave the kernels' instructions other than they were
+// (DESIGN.md §10.8).
+//
+// WG_KEPT_HEAD -- the kernel's head, in two parts with the in-state's shape between them: the static
+// and dynamic LDS, the working set W and the call's shape with its widths; then (WG_KEPT_CARVE) the
+// carve w, behind it MORE (k_batch_solve_drop's second carve; else empty), the resident budget and
+// wg_by_col's rule, decided once because the strides are the launch's.
+#define WG_KEPT_HEAD(a, sc)                                                                               \
+    extern __shared__ __attribute__((aligned(16))) double s_dyn[];                                        \
+    WG_SCRATCH(sc);                                                                                       \
+    double *const W = LDS ? s_dyn : (a).ws + (size_t)blockIdx.x * (size_t)(a).slice;                      \
+    const int n = (a).n, m = (a).m, Ns = 1 + n + m, N1 = Ns + m
+#define WG_KEPT_CARVE(a, MORE)                                                                            \
+    const BatchWork w = wg_carve(W, n, m);                                                                \
+    MORE;                                                                                                 \
+    const long long budget = (a).budget > 0 ? (a).budget : sx_batch_default_budget(n, m);                 \
+    const bool by_col = ((a).A_sc < 0 ? -(a).A_sc : (a).A_sc) <= ((a).A_sr < 0 ? -(a).A_sr : (a).A_sr)
+
+// WG_STATE_TEST -- the in-state of problem k, shape (n0, m0), tested before anything is indexed with
+// it: the phase (PH_OK, an expression in ph), both pivot counts >= 0, then the basis, which indexes d
+// (and, through the alias, T), so phase 2 knows no artificial variable.  Declares ph, q1, q2; the
+// result is the kernel's `good`, which GOOD declares (`bool good`) or names (k_batch_solve_st's).
+// The basis is loaded on the way: ROW is the statement for row i < rows, which reads base_in[i], stores
+// the working set's entry and ors an entry outside [0, lim) into bad (WG_BASE_ROW: the entry as it
+// is); MORE is a further statement that ors into bad.  Ends behind a barrier.
+#define WG_BASE_ROW(wk)                 \
+    {                                   \
+        const int bi = base_in[i];      \
+        (wk).base[i] = bi;              \
+        bad |= (unsigned)bi >= lim;     \
+    }
+#define WG_STATE_TEST(GOOD, in, PH_OK, n0, m0, rows, ROW, MORE)                                      \
+    const int ph = (in).phase[k];                                                                    \
+    const long long q1 = (in).pivots[2 * (size_t)k], q2 = (in).pivots[2 * (size_t)k + 1];            \
+    GOOD = (PH_OK) && q1 >= 0 && q2 >= 0;                                                            \
+    if (good) {                                                                                      \
+        const unsigned lim = ph == 1 ? (unsigned)((n0) + 2 * (m0)) : (unsigned)((n0) + (m0));        \
+        const int *base_in = (in).base + (size_t)k * (size_t)(m0);                                   \
+        int bad = 0;                                                                                 \
+        for (int i = threadIdx.x; i < (rows); i += SX_TILE) ROW                                      \
+        MORE                                                                                         \
+        good = !__syncthreads_or(bad);                                                               \
+    }
+
+// WG_DUAL_LOST -- is the row d of the carve wk, N wide, no longer dual feasible?  wg_solve's entering
+// selection and stop test, into `lost`.
+#define WG_DUAL_LOST(lost, wk, N)                                                                    \
+    do {                                                                                             \
+        double dmin;                                                                                 \
+        int e;                                                                                       \
+        wg_argmin((N) - 1, [&](int idx) { return (wk).d[1 + idx]; }, (wk).parts, sc, dmin, e);       \
+        lost = cmp_eps(dmin, 0.0) < 0;                                                               \
+    } while (0)
+
+// WG_SLACK_DOT -- into the new double `s`: row i of the slack block (row m: the slack entries of d)
+// times the m doubles staged in the pivot-row copy, S[i][.] v or y v: per element the chain of
+// wg_update_objective (512-element blocks from +0.0 by fma, added left to right).  Consecutive lanes
+// take consecutive rows: the odd ld keeps the gather conflict-free.  Declares row as well.
+#define WG_SLACK_DOT(s, i)                                                            \
+    const double *row = ((i) < m ? w.T + (size_t)(i) * w.ld : w.d) + 1 + n;           \
+    double s = 0.0;                                                                   \
+    for (int k0 = 0; k0 < m; k0 += SX_TILE) {                                         \
+        const int k1 = k0 + SX_TILE < m ? k0 + SX_TILE : m;                           \
+        double u = 0.0;                                                               \
+        for (int kk = k0; kk < k1; ++kk) u = fma(row[kk], w.prow[kk], u);             \
+        s = k0 == 0 ? u : s + u;                                                      \
+    }
+
+// WG_COLD_START -- the problem is built from A, b, c and solved as k_batch_solve_dev does, at the
+// sites every path shares: phase 1's tableau and canonical row, no pivot behind it.
+#define WG_COLD_START(t, dual)           \
+    do {                                 \
+        wg_build(w, src, by_col);        \
+        wg_update_objective(w, N1);      \
+        (t).p1 = (t).p2 = 0;             \
+        (t).ph2 = dual = false;          \
+    } while (0)
+
+// WG_KEPT_TAIL -- the loops behind every front, from where t and `dual` (the problem stands inside the
+// dual loop) say the problem stands: phase 1 behind t.p1 and phase 2's costs, or the dual loop behind
+// t.p2, then phase 2 at the same count.  What ends inside the dual loop leaves `dual` set.
+#define WG_KEPT_TAIL(t, dual)                                                          \
+    do {                                                                               \
+        if (!(t).ph2) {                                                                \
+            WG_PHASE1(t, w, N1, a.max_pivots, budget, (t).p1, sc);                     \
+            if ((t).ph2) {                                                             \
+                wg_phase2_costs(w, src);                                               \
+                wg_update_objective(w, Ns);                                            \
+                (t).p2 = 0;                                                            \
+            }                                                                          \
+        }                                                                              \
+        if ((t).ph2 && dual) {                                                         \
+            (t).status = wg_dual(w, a.max_pivots, budget, (t).p2, (t).p2, sc);         \
+            dual = (t).status != SX_FEASIBLE;                                          \
+        }                                                                              \
+        if ((t).ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, (t).p2, sc);   \
+    } while (0)
+
+// WG_KEPT_END -- the device entry's epilogue, then the working set into a.out (which may be a.in: the
+// workgroup has loaded all of its problem by then).  A problem whose state failed the tests (!good)
+// has every output cleared and phase 0; what ended inside the dual loop is saved as phase 3.
+#define WG_KEPT_END(t, good, dual)                                                   \
+    do {                                                                             \
+        wg_write_results(a, w, t, k, good);                                          \
+        WG_STORE_STATE(a.out, t, good, !(good) ? 0 : (dual) ? 3 : (t).ph2 ? 2 : 1);  \
     } while (0)
 
 // simplex_solve_batch: ragged problems packed by the host (A column-major, then b, then c), the RHS
@@ -631,20 +750,12 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_rag(BatchRagArgs a) {
 // pivots, then phase 2 from 0 with the call's costs; or phase 2 behind its saved pivots, or, with
 // a.recost, from 0 on the row of the call's costs made canonical for the saved basis.  No outcome
 // has a case of its own: selection writes nothing, so a state whose phase had ended ends again
-// without a pivot.  The state's phase, pivot counts and basis are tested before anything is indexed
-// with them; a problem that fails gets SX_BAD_STATE and cleared outputs.  Behind the device entry's
-// epilogue the working set is written to a.out (which may be a.in: the workgroup has loaded all of
-// its problem by then).
+// without a pivot.  The state is tested first (WG_STATE_TEST); a problem that fails gets SX_BAD_STATE
+// and cleared outputs.  The end is WG_KEPT_END's.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    WG_SCRATCH(sc);
-    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
-    const BatchWork w = wg_carve(W, n, m);
-    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
-    // wg_by_col's rule, decided once: the strides are the launch's
-    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    WG_KEPT_HEAD(a, sc);
+    WG_KEPT_CARVE(a, );
     const bool resume = a.in.T != nullptr;
     const int cells = m * Ns;  // (a working set holds them, so they fit an int)
     for (;;) {
@@ -659,21 +770,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
             wg_build(w, src, by_col);
             wg_update_objective(w, N1);
         } else {
-            const int ph = a.in.phase[k];
-            const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
-            good = (ph == 1 || ph == 2) && q1 >= 0 && q2 >= 0;
-            if (good) {
-                // the basis indexes d (and, through the alias, T): phase 2 knows no artificial variable
-                const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m) : (unsigned)(n + m);
-                const int *base_in = a.in.base + (size_t)k * (size_t)m;
-                int bad = 0;
-                for (int i = threadIdx.x; i < m; i += SX_TILE) {
-                    const int bi = base_in[i];
-                    w.base[i] = bi;
-                    bad |= (unsigned)bi >= lim;
-                }
-                good = !__syncthreads_or(bad);
-            }
+            WG_STATE_TEST(good, a.in, ph == 1 || ph == 2, n, m, m, WG_BASE_ROW(w), );
             if (good) {
                 // consecutive lanes walk the dense rows; the working set's stride is the odd ld
                 WG_LOAD_STATE(a.in);
@@ -700,9 +797,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
             }
             if (t.ph2) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
         }
-        // a problem whose state failed the tests has every output cleared
-        wg_write_results(a, w, t, k, good);
-        WG_STORE_STATE(a.out, t, good, !good ? 0 : t.ph2 ? 2 : 1);
+        WG_KEPT_END(t, good, false);
         __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
@@ -716,22 +811,16 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
 // feasible that is the warm start:
 // the new column and objective in wg_update_objective's order, the dual loop (wg_dual) from pivot 0
 // until the column is primal feasible, then phase 2 at the same count, which makes no pivot unless
-// rounding left an entry of d below -eps.  A phase-1 state, or a row that is not dual feasible (a
-// state that ended UNBOUNDED or was capped in phase 2), is a cold start: the problem is built from A,
-// b', c and solved as k_batch_solve_dev does, at the sites every path shares.  Without a.rerhs A and b
-// are not read; phase-1 and phase-2 states are k_batch_solve_st's resume and a phase-3 state
-// re-enters the dual loop behind its saved pivots.  The state's tests are k_batch_solve_st's with
-// phase 3 (the basis range is phase 2's).  What ends inside the dual loop is saved as phase 3.
+// rounding left an entry of d below -eps.  A phase-1 state, or a row that is not dual feasible
+// (WG_DUAL_LOST: a state that ended UNBOUNDED or was capped in phase 2), is a cold start from A, b', c
+// (WG_COLD_START).  Without a.rerhs A and b are not read; phase-1 and phase-2 states are
+// k_batch_solve_st's resume and a phase-3 state re-enters the dual loop behind its saved pivots.  The
+// state's tests are k_batch_solve_st's with phase 3 (the basis range is phase 2's); the loops and the
+// end are WG_KEPT_TAIL's and WG_KEPT_END's.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    WG_SCRATCH(sc);
-    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
-    const BatchWork w = wg_carve(W, n, m);
-    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
-    // wg_by_col's rule, decided once: the strides are the launch's
-    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    WG_KEPT_HEAD(a, sc);
+    WG_KEPT_CARVE(a, );
     const bool rerhs = a.rerhs != 0;
     const int cells = m * Ns;  // (a working set holds them, so they fit an int)
     for (;;) {
@@ -742,21 +831,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) 
                            rerhs ? a.b + (long long)k * a.b_sb : nullptr, a.b_si, a.c + (long long)k * a.c_sb, a.c_sj};
         TwoPhase t{SX_BAD_STATE, false, 0, 0};
         bool dual = false;  // the problem stands inside the dual loop
-        const int ph = a.in.phase[k];
-        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
-        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
-        if (good) {
-            // the basis indexes d (and, through the alias, T): phase 2 knows no artificial variable
-            const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m) : (unsigned)(n + m);
-            const int *base_in = a.in.base + (size_t)k * (size_t)m;
-            int bad = 0;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) {
-                const int bi = base_in[i];
-                w.base[i] = bi;
-                bad |= (unsigned)bi >= lim;
-            }
-            good = !__syncthreads_or(bad);
-        }
+        WG_STATE_TEST(bool good, a.in, ph >= 1 && ph <= 3, n, m, m, WG_BASE_ROW(w), );
         if (good) {
             bool cold = rerhs && ph == 1;
             if (!cold) {
@@ -770,55 +845,23 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) 
                 t.p2 = q2;
                 t.ph2 = ph >= 2;
                 dual = ph == 3;
-                if (rerhs) {
-                    // still dual feasible?  wg_solve's entering selection and stop test
-                    double dmin;
-                    int e;
-                    wg_argmin(Ns - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, sc, dmin, e);
-                    cold = cmp_eps(dmin, 0.0) < 0;
-                }
+                if (rerhs) WG_DUAL_LOST(cold, w, Ns);
             }
             if (cold) {
-                wg_build(w, src, by_col);
-                wg_update_objective(w, N1);
-                t.p1 = t.p2 = 0;
-                t.ph2 = dual = false;
+                WG_COLD_START(t, dual);
             } else if (rerhs) {
-                // T[i][0] = S[i][.] b' and, as row m, d[0] = y b': per element the chain of
-                // wg_update_objective (512-element blocks from +0.0 by fma, added left to right).
-                // Consecutive lanes take consecutive rows: the odd ld keeps the gather conflict-free.
+                // T[i][0] = S[i][.] b' and, as row m, d[0] = y b'
                 for (int i = threadIdx.x; i <= m; i += SX_TILE) {
-                    const double *row = (i < m ? w.T + (size_t)i * w.ld : w.d) + 1 + n;
-                    double s = 0.0;
-                    for (int k0 = 0; k0 < m; k0 += SX_TILE) {
-                        const int k1 = k0 + SX_TILE < m ? k0 + SX_TILE : m;
-                        double p = 0.0;
-                        for (int kk = k0; kk < k1; ++kk) p = fma(row[kk], w.prow[kk], p);
-                        s = k0 == 0 ? p : s + p;
-                    }
+                    WG_SLACK_DOT(s, i);
                     (i < m ? w.T[(size_t)i * w.ld] : w.d[0]) = s;
                 }
                 __syncthreads();
                 t.p2 = 0;
                 dual = true;
             }
-            if (!t.ph2) {
-                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
-                if (t.ph2) {
-                    wg_phase2_costs(w, src);
-                    wg_update_objective(w, Ns);
-                    t.p2 = 0;
-                }
-            }
-            if (t.ph2 && dual) {
-                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
-                dual = t.status != SX_FEASIBLE;
-            }
-            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+            WG_KEPT_TAIL(t, dual);
         }
-        // a problem whose state failed the tests has every output cleared
-        wg_write_results(a, w, t, k, good);
-        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
+        WG_KEPT_END(t, good, dual);
         __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
@@ -831,24 +874,18 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) 
 // Load: the dense in-state is walked at its stride 1 + n + m0 into the grown working set (odd ld of
 // the grown shape), old rows end in q entries of +0.0, d ends in +0.0 from 1 + n + m0 on, and the new
 // rows' slacks are basic.  A phase-1 state, or a row d that is not dual feasible, is a cold start from
-// A, b, c at the sites every path shares.  Warm start, per new row t: the multipliers f_i = the row's
+// A, b, c (WG_COLD_START).  Warm start, per new row t: the multipliers f_i = the row's
 // entry in the column of old row i's basic variable (+0.0 for a basic slack) are staged in colE, then
 // consecutive lanes take consecutive columns j -- the reads of T[i][j] are row-contiguous -- and
 // T[m0 + t][j] = the raw row's entry, then fma(-f_i, T[i][j], .) for i = 0 .. m0 - 1 in that order.
 // The new rows do not depend on each other, d is unchanged, pivots[0] is kept and pivots[1] = 0; then
-// the dual loop (wg_dual) from 0 and phase 2 at the same count.  Only rows m0 .. m of A and b are read
-// unless the problem is cold.  The state's tests are k_batch_solve_rhs's against the in-state's shape.
+// the dual loop from 0 and phase 2 at the same count (WG_KEPT_TAIL).  Only rows m0 .. m of A and b are
+// read unless the problem is cold.  The state's tests are k_batch_solve_rhs's against the in-state's shape.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    WG_SCRATCH(sc);
-    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    WG_KEPT_HEAD(a, sc);
     const int q = a.added, m0 = m - q, Ns0 = Ns - q, N10 = Ns0 + m0;  // the in-state's shape
-    const BatchWork w = wg_carve(W, n, m);
-    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
-    // wg_by_col's rule, decided once: the strides are the launch's
-    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    WG_KEPT_CARVE(a, );
     const int cells = m * Ns, cells0 = m0 * Ns0;  // (a working set holds them, so they fit an int)
     for (;;) {
         const unsigned k = wg_next(a.counter, sc);
@@ -857,31 +894,19 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a
                            a.c + (long long)k * a.c_sb, a.c_sj};
         TwoPhase t{SX_BAD_STATE, false, 0, 0};
         bool dual = false;  // the problem stands inside the dual loop
-        const int ph = a.in.phase[k];
-        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
-        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
-        if (good) {
-            // the in-state's own range: what is valid only for the grown shape is refused
-            const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m0) : (unsigned)(n + m0);
-            const int *base_in = a.in.base + (size_t)k * (size_t)m0;
-            int bad = 0;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) {
+        // the in-state's own range: what is valid only for the grown shape is refused
+        WG_STATE_TEST(
+            bool good, a.in, ph >= 1 && ph <= 3, n, m0, m,
+            {
                 const int bi = i < m0 ? base_in[i] : n + i;  // a new row's slack is basic
                 w.base[i] = bi;
                 bad |= i < m0 && (unsigned)bi >= lim;
-            }
-            good = !__syncthreads_or(bad);
-        }
+            }, );
         if (good) {
             bool cold = ph == 1;
             if (!cold) {
-                // consecutive lanes walk the dense rows of the in-state; the working set's stride is
-                // the grown shape's odd ld
-                const double *T_in = a.in.T + (size_t)k * (size_t)cells0;
-                for (int x = threadIdx.x; x < cells0; x += SX_TILE) {
-                    const int i = x / Ns0;
-                    w.T[(size_t)i * w.ld + (x - i * Ns0)] = T_in[x];
-                }
+                // the in-state's rows at the grown shape's odd ld
+                wg_load_T(w, a.in.T + (size_t)k * (size_t)cells0, Ns0, cells0);
                 for (int x = threadIdx.x; x < m0 * q; x += SX_TILE) {
                     const int i = x / q;
                     w.T[(size_t)i * w.ld + Ns0 + (x - i * q)] = 0.0;
@@ -889,17 +914,10 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a
                 const double *d_in = a.in.d + (size_t)k * (size_t)N10;
                 for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;
                 __syncthreads();
-                // still dual feasible?  wg_solve's entering selection and stop test, at the grown width
-                double dmin;
-                int e;
-                wg_argmin(Ns - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, sc, dmin, e);
-                cold = cmp_eps(dmin, 0.0) < 0;
+                WG_DUAL_LOST(cold, w, Ns);  // at the grown width
             }
             if (cold) {
-                wg_build(w, src, by_col);
-                wg_update_objective(w, N1);
-                t.p1 = t.p2 = 0;
-                t.ph2 = dual = false;
+                WG_COLD_START(t, dual);
             } else {
                 for (int r = m0; r < m; ++r) {
                     const double *Ar = src.A + (long long)r * src.A_sr;
@@ -923,23 +941,9 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a
                 t.p2 = 0;
                 t.ph2 = dual = true;
             }
-            if (!t.ph2) {
-                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
-                if (t.ph2) {
-                    wg_phase2_costs(w, src);
-                    wg_update_objective(w, Ns);
-                    t.p2 = 0;
-                }
-            }
-            if (t.ph2 && dual) {
-                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
-                dual = t.status != SX_FEASIBLE;
-            }
-            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+            WG_KEPT_TAIL(t, dual);
         }
-        // a problem whose state failed the tests has every output cleared
-        wg_write_results(a, w, t, k, good);
-        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
+        WG_KEPT_END(t, good, dual);
         __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
@@ -948,7 +952,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a
 // to the call's shape (n = n0 + p, m) and re-solved: k_batch_solve_rows with another front.  A kept
 // tableau is M [D b | D A | D] with the slack block S = M D (k_batch_solve_rhs), so the stored form of a
 // new structural column a is M D a = S a and its reduced cost y a - c_new, y the slack entries of d: the
-// re-rhs pass's two sums, once per new column.  S does not change, so the right-hand-side entry's
+// re-rhs pass's two sums (WG_SLACK_DOT), once per new column.  S does not change, so the right-hand-side entry's
 // identities hold on the grown state.
 // Load: the dense in-state is walked at its stride 1 + n0 + m into the grown working set (odd ld of the
 // grown shape); the structural block grows in the middle, so stored column j < 1 + n0 stays and the
@@ -961,19 +965,12 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a
 // phase 2 from 0 at the grown width, whatever its old status was.  A phase-3 state re-enters the dual
 // loop (wg_dual) from 0 while the grown d is still dual feasible, then phase 2 at the same count; a
 // phase-1 state, or a phase-3 state whose grown row is not dual feasible, is a cold start from A, b, c
-// at the sites every path shares.  The state's tests are k_batch_solve_rhs's against the in-state's
-// shape.
+// (WG_COLD_START).  The state's tests are k_batch_solve_rhs's against the in-state's shape.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    WG_SCRATCH(sc);
-    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    WG_KEPT_HEAD(a, sc);
     const int p = a.added, n0 = n - p, Ns0 = Ns - p, N10 = Ns0 + m;  // the in-state's shape
-    const BatchWork w = wg_carve(W, n, m);
-    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
-    // wg_by_col's rule, decided once: the strides are the launch's
-    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    WG_KEPT_CARVE(a, );
     const int cells = m * Ns, cells0 = m * Ns0;  // (a working set holds them, so they fit an int)
     for (;;) {
         const unsigned k = wg_next(a.counter, sc);
@@ -982,21 +979,14 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a
                            a.c + (long long)k * a.c_sb, a.c_sj};
         TwoPhase t{SX_BAD_STATE, false, 0, 0};
         bool dual = false;  // the problem stands inside the dual loop
-        const int ph = a.in.phase[k];
-        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
-        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
-        if (good) {
-            // the in-state's own range: what is valid only for the grown shape is refused
-            const unsigned lim = ph == 1 ? (unsigned)(n0 + 2 * m) : (unsigned)(n0 + m);
-            const int *base_in = a.in.base + (size_t)k * (size_t)m;
-            int bad = 0;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) {
+        // the in-state's own range: what is valid only for the grown shape is refused
+        WG_STATE_TEST(
+            bool good, a.in, ph >= 1 && ph <= 3, n0, m, m,
+            {
                 const int bi = base_in[i];
                 w.base[i] = bi >= n0 ? bi + p : bi;  // a slack moves up with its column
                 bad |= (unsigned)bi >= lim;
-            }
-            good = !__syncthreads_or(bad);
-        }
+            }, );
         if (good) {
             bool cold = ph == 1;
             if (!cold) {
@@ -1015,18 +1005,9 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a
                     const double *Ac = src.A + (long long)(n0 + c) * src.A_sc;
                     for (int i = threadIdx.x; i < m; i += SX_TILE) w.prow[i] = Ac[(long long)i * src.A_sr];
                     __syncthreads();  // (the first one also completes the load)
-                    // T[i][1 + n0 + c] = S[i][.] a and, as row m, d[1 + n0 + c] = y a - c_new: per element
-                    // the chain of wg_update_objective (512-element blocks from +0.0 by fma, added left
-                    // to right), as k_batch_solve_rhs sums S b'
+                    // T[i][1 + n0 + c] = S[i][.] a and, as row m, d[1 + n0 + c] = y a - c_new
                     for (int i = threadIdx.x; i <= m; i += SX_TILE) {
-                        const double *row = (i < m ? w.T + (size_t)i * w.ld : w.d) + 1 + n;
-                        double s = 0.0;
-                        for (int k0 = 0; k0 < m; k0 += SX_TILE) {
-                            const int k1 = k0 + SX_TILE < m ? k0 + SX_TILE : m;
-                            double u = 0.0;
-                            for (int kk = k0; kk < k1; ++kk) u = fma(row[kk], w.prow[kk], u);
-                            s = k0 == 0 ? u : s + u;
-                        }
+                        WG_SLACK_DOT(s, i);
                         if (i < m)
                             w.T[(size_t)i * w.ld + 1 + n0 + c] = s;
                         else
@@ -1034,42 +1015,19 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a
                     }
                     __syncthreads();  // prow is rewritten for the next column; T and d are complete behind the last
                 }
-                if (ph == 3) {
-                    // still dual feasible?  wg_solve's entering selection and stop test, at the grown width
-                    double dmin;
-                    int e;
-                    wg_argmin(Ns - 1, [&](int idx) { return w.d[1 + idx]; }, w.parts, sc, dmin, e);
-                    cold = cmp_eps(dmin, 0.0) < 0;
-                }
+                if (ph == 3) WG_DUAL_LOST(cold, w, Ns);  // at the grown width
             }
             if (cold) {
-                wg_build(w, src, by_col);
-                wg_update_objective(w, N1);
-                t.p1 = t.p2 = 0;
-                t.ph2 = dual = false;
+                WG_COLD_START(t, dual);
             } else {
                 t.p1 = q1;
                 t.p2 = 0;
                 t.ph2 = true;
                 dual = ph == 3;
             }
-            if (!t.ph2) {
-                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
-                if (t.ph2) {
-                    wg_phase2_costs(w, src);
-                    wg_update_objective(w, Ns);
-                    t.p2 = 0;
-                }
-            }
-            if (t.ph2 && dual) {
-                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
-                dual = t.status != SX_FEASIBLE;
-            }
-            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+            WG_KEPT_TAIL(t, dual);
         }
-        // a problem whose state failed the tests has every output cleared
-        wg_write_results(a, w, t, k, good);
-        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
+        WG_KEPT_END(t, good, dual);
         __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }
@@ -1212,8 +1170,8 @@ __device__ __forceinline__ int wg_drop(double *W, int n, int m, int kind, int q,
 // forced primal pivot needs a primal feasible column); column drops one of which is basic are warm only
 // while the loaded d is dual feasible (wg_solve's entering selection over d[1 .. Ns_in), once, before
 // the first drop), because the forced dual pivot keeps that; a forced selection without a candidate
-// makes the problem cold.  A cold problem is built from A, b, c of the reduced problem at the sites
-// every path shares.  The forced pivots belong to the load: pivots[0] is kept, pivots[1] starts at
+// makes the problem cold.  A cold problem is built from A, b, c of the reduced problem
+// (WG_COLD_START).  The forced pivots belong to the load: pivots[0] is kept, pivots[1] starts at
 // their number f, neither the cap nor the budget counts them, and the loops behind start at f: the dual
 // loop (wg_dual) for a phase-3 state and behind a forced dual pivot, then phase 2 at the same count;
 // phase 2 alone otherwise.  A basic slack's column is a unit column and a nonbasic column stands in no
@@ -1221,17 +1179,11 @@ __device__ __forceinline__ int wg_drop(double *W, int n, int m, int kind, int q,
 // hold on it.  The state's tests are k_batch_solve_rhs's against the in-state's shape.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-    WG_SCRATCH(sc);
-    double *const W = LDS ? s_dyn : a.ws + (size_t)blockIdx.x * (size_t)a.slice;
-    const int n = a.n, m = a.m, Ns = 1 + n + m, N1 = Ns + m;
+    WG_KEPT_HEAD(a, sc);
     const int kind = a.kind, q = a.dropped;
     const int n0 = kind == 0 ? n : n + q, m0 = kind == 0 ? m + q : m;  // the in-state's shape
     const int Ns0 = 1 + n0 + m0, N10 = Ns0 + m0;
-    const BatchWork w = wg_carve(W, n, m), w0 = wg_carve(W, n0, m0);
-    const long long budget = a.budget > 0 ? a.budget : sx_batch_default_budget(n, m);
-    // wg_by_col's rule, decided once: the strides are the launch's
-    const bool by_col = (a.A_sc < 0 ? -a.A_sc : a.A_sc) <= (a.A_sr < 0 ? -a.A_sr : a.A_sr);
+    WG_KEPT_CARVE(a, const BatchWork w0 = wg_carve(W, n0, m0));
     const int cells = m * Ns, cells0 = m0 * Ns0;  // (a working set holds them, so they fit an int)
     for (;;) {
         const unsigned k = wg_next(a.counter, sc);
@@ -1240,36 +1192,20 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a
                            a.c + (long long)k * a.c_sb, a.c_sj};
         TwoPhase t{SX_BAD_STATE, false, 0, 0};
         bool dual = false;  // the problem stands inside the dual loop
-        const int ph = a.in.phase[k];
-        const long long q1 = a.in.pivots[2 * (size_t)k], q2 = a.in.pivots[2 * (size_t)k + 1];
         const int *ix = a.idx + (size_t)k * (size_t)q;
-        bool good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
-        if (good) {
-            // the in-state's own range, and the list: strictly ascending inside that shape
-            const unsigned lim = ph == 1 ? (unsigned)(n0 + 2 * m0) : (unsigned)(n0 + m0);
-            const int *base_in = a.in.base + (size_t)k * (size_t)m0;
-            int bad = 0;
-            for (int i = threadIdx.x; i < m0; i += SX_TILE) {
-                const int bi = base_in[i];
-                w0.base[i] = bi;
-                bad |= (unsigned)bi >= lim;
-            }
+        // the in-state's own range, and the list: strictly ascending inside that shape
+        WG_STATE_TEST(
+            bool good, a.in, ph >= 1 && ph <= 3, n0, m0, m0, WG_BASE_ROW(w0),
             for (int j = threadIdx.x; j < q; j += SX_TILE) {
                 const int v = ix[j];
                 bad |= (unsigned)v >= (unsigned)(kind == 0 ? m0 : n0) || (j > 0 && ix[j - 1] >= v);
-            }
-            good = !__syncthreads_or(bad);
-        }
+            });
         if (good) {
             bool cold = ph == 1;
             int forced = 0;
             if (!cold) {
-                // consecutive lanes walk the dense rows of the in-state at its own shape
-                const double *T_in = a.in.T + (size_t)k * (size_t)cells0;
-                for (int x = threadIdx.x; x < cells0; x += SX_TILE) {
-                    const int i = x / Ns0;
-                    w0.T[(size_t)i * w0.ld + (x - i * Ns0)] = T_in[x];
-                }
+                // the in-state at its own shape
+                wg_load_T(w0, a.in.T + (size_t)k * (size_t)cells0, Ns0, cells0);
                 const double *d_in = a.in.d + (size_t)k * (size_t)N10;
                 for (int j = threadIdx.x; j < N10; j += SX_TILE) w0.d[j] = d_in[j];
                 __syncthreads();
@@ -1279,11 +1215,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a
                     if (kind == 0) {
                         cold = basic != q;
                     } else if (basic > 0) {
-                        // still dual feasible?  wg_solve's entering selection and stop test
-                        double dmin;
-                        int e;
-                        wg_argmin(Ns0 - 1, [&](int idx) { return w0.d[1 + idx]; }, w0.parts, sc, dmin, e);
-                        cold = cmp_eps(dmin, 0.0) < 0;
+                        WG_DUAL_LOST(cold, w0, Ns0);  // at the in-state's width, before the first drop
                     }
                 }
                 if (!cold) {
@@ -1292,33 +1224,16 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a
                 }
             }
             if (cold) {
-                wg_build(w, src, by_col);
-                wg_update_objective(w, N1);
-                t.p1 = t.p2 = 0;
-                t.ph2 = dual = false;
+                WG_COLD_START(t, dual);
             } else {
                 t.p1 = q1;
                 t.p2 = forced;
                 t.ph2 = true;
                 dual = ph == 3 || (kind == 1 && forced > 0);
             }
-            if (!t.ph2) {
-                WG_PHASE1(t, w, N1, a.max_pivots, budget, t.p1, sc);
-                if (t.ph2) {
-                    wg_phase2_costs(w, src);
-                    wg_update_objective(w, Ns);
-                    t.p2 = 0;
-                }
-            }
-            if (t.ph2 && dual) {
-                t.status = wg_dual(w, a.max_pivots, budget, t.p2, t.p2, sc);
-                dual = t.status != SX_FEASIBLE;
-            }
-            if (t.ph2 && !dual) WG_PHASE2(t, w, Ns, a.max_pivots, budget, t.p2, sc);
+            WG_KEPT_TAIL(t, dual);
         }
-        // a problem whose state failed the tests has every output cleared
-        wg_write_results(a, w, t, k, good);
-        WG_STORE_STATE(a.out, t, good, !good ? 0 : dual ? 3 : t.ph2 ? 2 : 1);
+        WG_KEPT_END(t, good, dual);
         __syncthreads();  // the next problem overwrites the working set and sc.k
     }
 }

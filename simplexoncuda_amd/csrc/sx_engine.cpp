@@ -2615,46 +2615,58 @@ static int batch_device_enqueue(const simplex_batch_device_t *args, const BatchD
     return 0;
 }
 
-// The one-shape entry (k_batch_solve_dev).
-int simplex_solve_batch_device(const simplex_batch_device_t *args) {
+// Plan, return early, enqueue: `a` carries the entry's own arguments, and its BatchDevArgs part
+// becomes the plan's.
+extern "C++" template <class Args>
+static int batch_device_run(const simplex_batch_device_t *args, BatchEntry entry, bool own_ok, bool c_only, Args a,
+                            int wn = 0, int wm = 0) {
     BatchDevPlan p;
-    const int rc = batch_device_plan(args, BatchEntry::Dev, true, false, &p);
+    const int rc = batch_device_plan(args, entry, own_ok, c_only, &p, wn, wm);
     if (rc != 0 || p.grid == 0) return rc;
-    return batch_device_enqueue(args, p, p.a);
+    static_cast<BatchDevArgs &>(a) = p.a;
+    return batch_device_enqueue(args, p, a);
 }
 
-// The state entry: a saved state per problem, loaded from `in` and written to `out` by the kernel
-// (k_batch_solve_st).  A state's contents are device data, so the kernel tests them (SX_BAD_STATE).
+// The one-shape entry (k_batch_solve_dev).
+int simplex_solve_batch_device(const simplex_batch_device_t *args) {
+    return batch_device_run(args, BatchEntry::Dev, true, false, BatchDevArgs{});
+}
+
+// The entries on a saved state per problem, loaded from `in` and written to `out` by the kernel.  A
+// state's contents are device data, so the kernel tests them (SX_BAD_STATE); the host tests the pointers.
 static bool state_complete(const simplex_batch_state_t *s) {
     return s == nullptr ||
            (s->T != nullptr && s->d != nullptr && s->base != nullptr && s->phase != nullptr && s->pivots != nullptr);
 }
+// the kernel's view of a state; no state: every pointer null
+static BatchState batch_state(const simplex_batch_state_t *s) {
+    if (s == nullptr) return BatchState{nullptr, nullptr, nullptr, nullptr, nullptr};
+    return BatchState{s->T, s->d, s->base, s->phase, s->pivots};
+}
+// `in` is there and both states are complete
+static bool kept_states_ok(const simplex_batch_state_t *in, const simplex_batch_state_t *out) {
+    return in != nullptr && state_complete(in) && state_complete(out);
+}
+// the two states share an array
+static bool states_share(const simplex_batch_state_t *in, const simplex_batch_state_t *out) {
+    return in != nullptr && out != nullptr &&
+           (out->T == in->T || out->d == in->d || out->base == in->base || out->phase == in->phase ||
+            out->pivots == in->pivots);
+}
 
+// The state entry (k_batch_solve_st): with `in` the call is a resume and reads c alone.
 int simplex_solve_batch_device_state(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
                                      const simplex_batch_state_t *out, int recost) {
-    BatchDevPlan p;
-    const int rc = batch_device_plan(args, BatchEntry::St, state_complete(in) && state_complete(out), in != nullptr, &p);
-    if (rc != 0 || p.grid == 0) return rc;
-    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    return batch_device_enqueue(args, p,
-                                BatchStArgs{p.a, in ? BatchState{in->T, in->d, in->base, in->phase, in->pivots} : none,
-                                            out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
-                                            recost != 0});
+    return batch_device_run(args, BatchEntry::St, state_complete(in) && state_complete(out), in != nullptr,
+                            BatchStArgs{{}, batch_state(in), batch_state(out), recost != 0});
 }
 
 // The right-hand-side entry (k_batch_solve_rhs): the state entry's body with `in` required; A and b
 // are the source only with rerhs, else the call is a resume and reads c alone.
 int simplex_solve_batch_device_rhs(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
                                    const simplex_batch_state_t *out, int rerhs) {
-    BatchDevPlan p;
-    const int rc = batch_device_plan(args, BatchEntry::Rhs, in != nullptr && state_complete(in) && state_complete(out),
-                                     rerhs == 0, &p);
-    if (rc != 0 || p.grid == 0) return rc;
-    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    return batch_device_enqueue(args, p,
-                                BatchRhsArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
-                                             out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
-                                             rerhs != 0});
+    return batch_device_run(args, BatchEntry::Rhs, kept_states_ok(in, out), rerhs == 0,
+                            BatchRhsArgs{{}, batch_state(in), batch_state(out), rerhs != 0});
 }
 
 // The rows entry (k_batch_solve_rows): args is the grown problem, `in` the kept state of its first
@@ -2662,18 +2674,8 @@ int simplex_solve_batch_device_rhs(const simplex_batch_device_t *args, const sim
 int simplex_solve_batch_device_rows(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
                                     const simplex_batch_state_t *out, int added) {
     if (args != nullptr && args->count >= 0 && (added < 1 || added >= args->m)) return -3;
-    const bool shared = in != nullptr && out != nullptr &&
-                        (out->T == in->T || out->d == in->d || out->base == in->base || out->phase == in->phase ||
-                         out->pivots == in->pivots);
-    BatchDevPlan p;
-    const int rc = batch_device_plan(args, BatchEntry::Rows,
-                                     in != nullptr && state_complete(in) && state_complete(out) && !shared, false, &p);
-    if (rc != 0 || p.grid == 0) return rc;
-    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    return batch_device_enqueue(args, p,
-                                BatchRowsArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
-                                              out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
-                                              added});
+    return batch_device_run(args, BatchEntry::Rows, kept_states_ok(in, out) && !states_share(in, out), false,
+                            BatchRowsArgs{{}, batch_state(in), batch_state(out), added});
 }
 
 // The columns entry (k_batch_solve_cols): args is the grown problem, `in` the kept state of its first
@@ -2681,18 +2683,8 @@ int simplex_solve_batch_device_rows(const simplex_batch_device_t *args, const si
 int simplex_solve_batch_device_cols(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
                                     const simplex_batch_state_t *out, int added) {
     if (args != nullptr && args->count >= 0 && (added < 1 || added >= args->n)) return -3;
-    const bool shared = in != nullptr && out != nullptr &&
-                        (out->T == in->T || out->d == in->d || out->base == in->base || out->phase == in->phase ||
-                         out->pivots == in->pivots);
-    BatchDevPlan p;
-    const int rc = batch_device_plan(args, BatchEntry::Cols,
-                                     in != nullptr && state_complete(in) && state_complete(out) && !shared, false, &p);
-    if (rc != 0 || p.grid == 0) return rc;
-    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    return batch_device_enqueue(args, p,
-                                BatchColsArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
-                                              out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
-                                              added});
+    return batch_device_run(args, BatchEntry::Cols, kept_states_ok(in, out) && !states_share(in, out), false,
+                            BatchColsArgs{{}, batch_state(in), batch_state(out), added});
 }
 
 // The drop entry (k_batch_solve_drop): args is the reduced problem, `in` the kept state of the problem
@@ -2707,19 +2699,9 @@ int simplex_solve_batch_device_drop(const simplex_batch_device_t *args, const si
         n0 = kind == 0 ? args->n : (int)grown;
         m0 = kind == 0 ? (int)grown : args->m;
     }
-    const bool shared = in != nullptr && out != nullptr &&
-                        (out->T == in->T || out->d == in->d || out->base == in->base || out->phase == in->phase ||
-                         out->pivots == in->pivots);
-    BatchDevPlan p;
-    const int rc = batch_device_plan(args, BatchEntry::Drop,
-                                     in != nullptr && idx != nullptr && state_complete(in) && state_complete(out) && !shared,
-                                     false, &p, n0, m0);
-    if (rc != 0 || p.grid == 0) return rc;
-    const BatchState none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    return batch_device_enqueue(args, p,
-                                BatchDropArgs{p.a, BatchState{in->T, in->d, in->base, in->phase, in->pivots},
-                                              out ? BatchState{out->T, out->d, out->base, out->phase, out->pivots} : none,
-                                              kind, dropped, idx});
+    return batch_device_run(args, BatchEntry::Drop,
+                            idx != nullptr && kept_states_ok(in, out) && !states_share(in, out), false,
+                            BatchDropArgs{{}, batch_state(in), batch_state(out), kind, dropped, idx}, n0, m0);
 }
 
 // The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.

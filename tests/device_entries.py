@@ -4,6 +4,8 @@ optional outputs left NULL, a caller-made workspace.  ctypes over _lib.BatchDevi
 
   workspace                    simplex_batch_device_workspace
   batch_device                 simplex_solve_batch_device, simplex_solve_batch_device_ragged
+  kept_call                    simplex_solve_batch_device_state, _rhs, _rows, _cols, _drop
+                               (state_call, rhs_call, rows_call, cols_call, drop_call)
   solve_device                 simplex_solve_device
   build_phase1_device          simplex_dev_build_phase1_device
 
@@ -111,14 +113,13 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def batch_device(A, b, c, n, m, count, x=ALLOC, base=ALLOC, objrow=ALLOC, row_width=ALLOC, max_pivots=-1, ws=None,
-                 ws_bytes=None, n_k=None, m_k=None, order=None, ragged=False):
-    """simplex_solve_batch_device, or with ragged=True (or n_k / m_k / order) the ragged entry; A, b, c
-    are Srcs with strides (batch, row, column), (batch, i), (batch, j); ws: a uint8 tensor whose
-    first ws_bytes (default: all of it) are the workspace, None: exactly the query's bytes.  Waits for
-    the launch.  Returns the output tensors (None where NULL was passed), evicted and rc"""
-    lib = _lib.load()
-    ragged = ragged or n_k is not None or m_k is not None or order is not None
+def call_args(n, m, count, A, b, c, x=ALLOC, base=ALLOC, objrow=ALLOC, row_width=ALLOC, max_pivots=-1, ws=None,
+              ws_bytes=None, ws_shape=None, call_count=None):
+    """What every caller of a batch entry builds: the outputs, pre-filled with SENTINEL (None where NULL
+    is passed), the workspace (o.ws) and the BatchDeviceT.  A, b, c are Srcs with strides (batch, row,
+    column), (batch, i), (batch, j); A or b None: NULL.  ws: a uint8 tensor whose first ws_bytes
+    (default: all of it) are the workspace, None: exactly the query's bytes for ws_shape (default:
+    (n, m)).  call_count: the count passed to the entry (default: count).  Returns (o, args)"""
     N1 = 1 + n + 2 * m
     o = SimpleNamespace(
         status=_out(ALLOC, (count,), torch.int32), pivots=_out(ALLOC, (count, 2), torch.int64),
@@ -126,20 +127,32 @@ def batch_device(A, b, c, n, m, count, x=ALLOC, base=ALLOC, objrow=ALLOC, row_wi
         base=_out(base, (count, m), torch.int32), objrow=_out(objrow, (count, N1), torch.float64),
         row_width=_out(row_width, (count,), torch.int32), evicted=_out(ALLOC, (1,), torch.int32))
     if ws is None:
-        ws = torch.empty(workspace(n, m, count), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(workspace(*(ws_shape or (n, m)), count), dtype=torch.uint8, device="cuda")
     if ws_bytes is None:
         ws_bytes = ws.numel()
     assert ws.dtype == torch.uint8 and 0 <= ws_bytes <= ws.numel()
+    src = dict(c=c.ptr, c_sb=c.strides[0], c_sj=c.strides[1])
+    if A is not None:
+        src.update(A=A.ptr, A_sb=A.strides[0], A_sr=A.strides[1], A_sc=A.strides[2])
+    if b is not None:
+        src.update(b=b.ptr, b_sb=b.strides[0], b_si=b.strides[1])
     args = _lib.BatchDeviceT(
-        n=n, m=m, count=count,
-        A=A.ptr, A_sb=A.strides[0], A_sr=A.strides[1], A_sc=A.strides[2],
-        b=b.ptr, b_sb=b.strides[0], b_si=b.strides[1],
-        c=c.ptr, c_sb=c.strides[0], c_sj=c.strides[1],
-        max_pivots=max_pivots,
+        n=n, m=m, count=count if call_count is None else call_count, max_pivots=max_pivots,
         status=o.status.data_ptr(), pivots=o.pivots.data_ptr(), opt=o.opt.data_ptr(), x=_ptr(o.x), base=_ptr(o.base),
         objrow=_ptr(o.objrow), row_width=_ptr(o.row_width), evicted=o.evicted.data_ptr(),
         workspace=ws.data_ptr(), workspace_bytes=ws_bytes,
-        stream=torch.cuda.current_stream().cuda_stream)
+        stream=torch.cuda.current_stream().cuda_stream, **src)
+    o.ws = ws
+    return o, args
+
+
+def batch_device(A, b, c, n, m, count, n_k=None, m_k=None, order=None, ragged=False, **kw):
+    """simplex_solve_batch_device, or with ragged=True (or n_k / m_k / order) the ragged entry; the
+    sources, optional outputs, max_pivots and workspace are call_args'.  Waits for the launch.  Returns
+    the output tensors (None where NULL was passed), evicted and rc"""
+    lib = _lib.load()
+    ragged = ragged or n_k is not None or m_k is not None or order is not None
+    o, args = call_args(n, m, count, A, b, c, **kw)
     if ragged:
         full = lambda v: torch.full((count,), v, dtype=torch.int32, device="cuda")  # noqa: E731
         n_k = full(n) if n_k is None else n_k
@@ -150,8 +163,48 @@ def batch_device(A, b, c, n, m, count, x=ALLOC, base=ALLOC, objrow=ALLOC, row_wi
     else:
         o.rc = lib.simplex_solve_batch_device(ctypes.byref(args))
     torch.cuda.current_stream().synchronize()
-    o.ws = ws
     return o
+
+
+def kept_call(entry, n, m, count, A, b, c, state_in, state_out, *extra, **kw):
+    """one call of an entry on a kept state, for what the sx wrappers never pass: a NULL `out` (or `in`),
+    NULL A and b, the optional outputs left NULL, a negative count, a workspace sized for the wrong
+    shape.  state_in / state_out are sx.BatchState or None (NULL), `extra` the entry's arguments behind
+    them; the rest is call_args'.  Waits for the launch.  Returns the output tensors (None where NULL
+    was passed) and rc"""
+    o, args = call_args(n, m, count, A, b, c, **kw)
+    sin = None if state_in is None else state_in._struct()
+    sout = None if state_out is None else state_out._struct()
+    o.rc = getattr(_lib.load(), entry)(ctypes.byref(args), None if sin is None else ctypes.byref(sin),
+                                       None if sout is None else ctypes.byref(sout), *extra)
+    torch.cuda.current_stream().synchronize()
+    return o
+
+
+def state_call(n, m, count, c, A=None, b=None, state_in=None, state_out=None, recost=False, **kw):
+    return kept_call("simplex_solve_batch_device_state", n, m, count, A, b, c, state_in, state_out, 1 if recost else 0,
+                     **kw)
+
+
+def rhs_call(n, m, count, c, state_in, A=None, b=None, state_out=None, rerhs=False, **kw):
+    return kept_call("simplex_solve_batch_device_rhs", n, m, count, A, b, c, state_in, state_out, 1 if rerhs else 0, **kw)
+
+
+def rows_call(n, m, count, A, b, c, state_in, added, state_out=None, **kw):
+    """on the grown shape (n, m); state_in has the shape (n, m - added)"""
+    return kept_call("simplex_solve_batch_device_rows", n, m, count, A, b, c, state_in, state_out, added, **kw)
+
+
+def cols_call(n, m, count, A, b, c, state_in, added, state_out=None, **kw):
+    """on the grown shape (n, m); state_in has the shape (n - added, m)"""
+    return kept_call("simplex_solve_batch_device_cols", n, m, count, A, b, c, state_in, state_out, added, **kw)
+
+
+def drop_call(n, m, count, A, b, c, state_in, kind, idx, state_out=None, ws_shape=None, **kw):
+    """on the reduced shape (n, m); idx is a dense int32 [count, q] device tensor, and the workspace is
+    sized for the in-state's shape unless ws_shape says otherwise"""
+    return kept_call("simplex_solve_batch_device_drop", n, m, count, A, b, c, state_in, state_out, kind, idx.shape[1],
+                     idx.data_ptr(), ws_shape=ws_shape or (state_in.n, state_in.m), **kw)
 
 
 def as_batch_tensors(o, n_k=None, m_k=None, keep=None):

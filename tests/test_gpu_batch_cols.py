@@ -1,5 +1,5 @@
 """A kept batch state grown by new structural columns (simplex_solve_batch_device_cols, sx_batch.hip
-k_batch_solve_cols) through sx.add_cols_batch_tensors, and through a ctypes caller (cols_entry.py) for
+k_batch_solve_cols) through sx.add_cols_batch_tensors, and through a ctypes caller (device_entries.cols_call) for
 what that never passes.  Needs an MI355X.
 
 Everything is compared bit for bit, without a tolerance, against batch_cols_refs.py: the entry restated
@@ -19,8 +19,7 @@ from batch_refs import same_as_refs, same_tensors, tensors
 from batch_rhs_refs import negated_rhs, ref_rhs, ref_rhs_resume, scaled_rhs
 from batch_rows_refs import grow, ref_rows
 from batch_state_refs import (bits, mixed_instances, ref_state, same_as_state_refs, save_instances, state_tensors)
-from cols_entry import cols_call
-from device_entries import dense
+from device_entries import cols_call, dense
 
 pytestmark = pytest.mark.gpu
 

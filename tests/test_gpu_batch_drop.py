@@ -1,6 +1,6 @@
 """Rows or columns taken out of a kept batch state (simplex_solve_batch_device_drop, sx_batch.hip
 k_batch_solve_drop) through sx.drop_rows_batch_tensors and sx.drop_cols_batch_tensors, and through a ctypes
-caller (drop_entry.py) for what those never pass.  Needs an MI355X.
+caller (device_entries.drop_call) for what those never pass.  Needs an MI355X.
 
 Everything is compared bit for bit, without a tolerance, against batch_drop_refs.py: the entry restated
 from the oracle's argmin, ratio and pivot, batch_rhs_refs' dual loop and batch_state_refs._run
@@ -21,8 +21,7 @@ from batch_refs import same_as_refs, same_tensors, tensors
 from batch_rhs_refs import ref_rhs, ref_rhs_resume
 from batch_rows_refs import make_row, ref_rows
 from batch_state_refs import bits, ref_state, same_as_state_refs, state_tensors, warm_instances
-from device_entries import dense
-from drop_entry import drop_call
+from device_entries import dense, drop_call
 
 pytestmark = pytest.mark.gpu
 

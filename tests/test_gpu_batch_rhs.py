@@ -1,6 +1,6 @@
 """A kept batch state re-solved for a new right-hand side (simplex_solve_batch_device_rhs, sx_batch.hip
 k_batch_solve_rhs) through sx.resume_batch_tensors(state, c, A=, b=), and through a ctypes caller
-(rhs_entry.py) for what that never passes.  Needs an MI355X.
+(device_entries.rhs_call) for what that never passes.  Needs an MI355X.
 
 Everything is compared bit for bit, without a tolerance, against batch_rhs_refs.py: the entry
 restated from the oracle's argmin, ratio, gemv_partials and apply_update (test_batch_rhs_host.py
@@ -17,8 +17,7 @@ from batch_rhs_refs import (CAP_SHAPE, PHASE2_CAP, PHASE2_CAP_SHAPE, RHS_CAPS, R
                             ladder_cases, negated_rhs, ref_rhs, ref_rhs_resume, rhs_instances, scaled_batch)
 from batch_state_refs import (bits, many_instances, mixed_instances, ref_resume, ref_state, same_as_state_refs,
                               state_tensors)
-from device_entries import dense
-from rhs_entry import rhs_call
+from device_entries import dense, rhs_call
 
 pytestmark = pytest.mark.gpu
 

@@ -1,5 +1,5 @@
 """A kept batch state grown by new constraint rows (simplex_solve_batch_device_rows, sx_batch.hip
-k_batch_solve_rows) through sx.add_rows_batch_tensors, and through a ctypes caller (rows_entry.py) for
+k_batch_solve_rows) through sx.add_rows_batch_tensors, and through a ctypes caller (device_entries.rows_call) for
 what that never passes.  Needs an MI355X.
 
 Everything is compared bit for bit, without a tolerance, against batch_rows_refs.py: the entry
@@ -17,8 +17,7 @@ from batch_rhs_refs import ref_rhs, ref_rhs_resume, scaled_rhs
 from batch_rows_refs import (CAP_SHAPE, KINDS, ROWS_CAPS, THETAS, cuts_off, grow, make_row, ref_rows, rows_instances,
                              rows_shapes, want_batch)
 from batch_state_refs import (bits, many_instances, mixed_instances, ref_state, same_as_state_refs, state_tensors)
-from device_entries import dense
-from rows_entry import rows_call
+from device_entries import dense, rows_call
 
 pytestmark = pytest.mark.gpu
 

@@ -1,6 +1,6 @@
 """The batch state (simplex_solve_batch_device_state, sx_batch.hip k_batch_solve_st) through
 sx.solve_batch_tensors(keep_state=True) and sx.resume_batch_tensors, and through a ctypes caller
-(state_entry.py) for what those never pass.  Needs an MI355X.
+(device_entries.state_call) for what those never pass.  Needs an MI355X.
 
 Everything is compared bit for bit, without a tolerance, against batch_state_refs.py: the state
 restated from the oracle's build_phase1, update_objective and solve (test_batch_state_host.py shows
@@ -21,8 +21,7 @@ from batch_state_refs import (BAD_STATE_PHASE1_CAP, CAP_SHAPES, CAPS, LADDER_CAP
                               cap_instances, cap_value, eviction_instances, ladder_instances, many_instances,
                               mixed_instances, ref_resume, ref_state, same_as_state_refs, save_instances,
                               state_tensors, structured_instances, warm_costs, warm_instances)
-from device_entries import SENTINEL, dense
-from state_entry import state_call
+from device_entries import SENTINEL, dense, state_call
 
 pytestmark = pytest.mark.gpu
 

@@ -18,7 +18,6 @@ import torch
 import device_entries as de
 import oracle
 import simplexoncuda_amd as sx
-import state_entry as se
 import test_gpu_batch_device as tbd
 import test_gpu_batch_ragged as rag
 import test_gpu_solve_device as tsd
@@ -58,8 +57,8 @@ def test_batch_optional_outputs(gpu, n, m, B):
     state = sx.BatchState.empty(B, n, m, torch.device("cuda"))
     entries = {"one shape": lambda **kw: de.batch_device(A, b, c, n, m, B, **kw),
                "ragged": lambda **kw: de.batch_device(A, b, c, n, m, B, ragged=True, **kw),
-               "state, out NULL": lambda **kw: se.state_call(n, m, B, c, A, b, **kw),
-               "state, out given": lambda **kw: se.state_call(n, m, B, c, A, b, state_out=state, **kw)}
+               "state, out NULL": lambda **kw: de.state_call(n, m, B, c, A, b, **kw),
+               "state, out given": lambda **kw: de.state_call(n, m, B, c, A, b, state_out=state, **kw)}
     for entry, call in entries.items():
         full = call()
         assert full.rc == 0, entry
