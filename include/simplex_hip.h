@@ -464,6 +464,61 @@ int simplex_solve_batch_device_drop(const simplex_batch_device_t *args,
                                     int dropped /* q >= 1, the same for every problem */,
                                     const int *idx /* device, int32 [count][dropped], dense */);
 
+/* ---- device batch state: branching (many children per kept parent, bound rows) ---- */
+/* Branch kept states: child k continues the kept state of problem parent[k] with one more bound row.
+ * args->n, args->m and args->count = C are the CHILDREN's shape and number: every output, `out` and the
+ * workspace simplex_batch_device_workspace(n, m, C) are that shape's.  The problem data are not repeated
+ * per child: args->A, b and c hold `roots` = R problems of mA = m - depth rows, A [R][mA][n], b [R][mA],
+ * c [R][n] through the struct's strides (a batch stride may be 0 only when R == 1), read in place, and
+ * child k is the LP of problem root[k] followed by the depth = q rows
+ *   coef[k][t] * x_{var[k][t]} <= rhs[k][t],   t = 0 .. q-1,
+ * given as triples, dense and row-major on the device.  The first q-1 of them must be the rows the state of
+ * parent[k] was solved with, behind root[k]'s own (the caller's contract, as with
+ * simplex_solve_batch_device_rows); the last one is new.  `in` holds `parents` = P problems of shape
+ * (n, m-1); it is only read, so any number of children may name one parent.
+ * Per child the call is simplex_solve_batch_device_rows with added = 1 on the explicit inputs -- the
+ * in-state of problem parent[k], and the dense grown A whose bound rows hold coef at column var and +0.0
+ * elsewhere, with b ending in rhs: status, pivots, opt, x, base, objrow, row_width and the out-state are
+ * that call's bit for bit, and so are its warm and cold decisions.
+ *   cold start -- the parent is in phase 1, or the eps-argmin of its d[1 .. 1+n+m-1) followed by +0.0
+ *   compares below zero: the phase-1 tableau of root[k]'s rows plus all q bound rows is built and solved as
+ *   simplex_solve_batch_device does, a row with compare(b_i, 0) < 0 negated across all its entries;
+ *   warm start -- otherwise.  With v = var[k][q-1], the raw row is R[0] = rhs[k][q-1], R[1+j] = (j == v) ?
+ *   coef[k][q-1] : +0.0, R[1+n+i] = (i == m-1) ? 1.0 : +0.0, the multipliers are f_i = (base[i] == v) ?
+ *   coef[k][q-1] : +0.0, and T[m-1][j] starts at R[j] and takes fma(-f_i, T[i][j], .) for i = 0 .. m-2 in
+ *   that order, the whole chain (the zero multipliers decide signed zeros).  pivots[0] is kept,
+ *   pivots[1] = 0; then the dual loop from 0 and phase 2 at the same count.
+ * Tested on the device before anything is indexed with the values: parent[k] in [0, P), root[k] in [0, R),
+ * every var[k][t] in [0, n), then the in-state of parent[k] as simplex_solve_batch_device_rows tests it
+ * against the shape (n, m-1).  A child that fails gets SIMPLEX_BAD_STATE with
+ * simplex_solve_batch_device_state's cleared outputs and out->phase 0; the other children are not
+ * affected.  coef and rhs are data, as the entries of A are.
+ * The out-state is a state of every state entry and of this one for the shape (n, m); a child stopped
+ * inside the dual loop is kept in phase 3.  With out NULL no state is kept: the form for strong branching,
+ * where max_pivots bounds each probe; a probe stopped by it inside the dual loop has opt NaN, and its
+ * dual bound is objrow[k][0].
+ * Returns, decided before any device is touched: -1 args NULL or count < 0; -3 a shape (n, m) of class 0,
+ * depth < 1, depth >= m, roots < 1 or parents < 1; 0 for count == 0; -2 br or one of its five arrays
+ * NULL, a required output NULL, in NULL or incomplete, out incomplete or sharing a member pointer with
+ * in, A, b or c NULL; -4 a zero stride of A, b or c along a dimension longer than 1 (the batch dimension
+ * has length R, the row dimension mA); -5 the workspace.  The call only enqueues two small memsets and one
+ * launch on `stream`. */
+typedef struct {
+    int roots;          /* R: problems held in args->A, b, c */
+    int parents;        /* P: problems held in the in-state */
+    int depth;          /* q >= 1: bound rows per child; the last one is new */
+    const int *root;    /* [count]      child k's problem is root[k] */
+    const int *parent;  /* [count]      child k continues in-state problem parent[k] */
+    const int *var;     /* [count, q]   dense, row-major */
+    const double *coef; /* [count, q] */
+    const double *rhs;  /* [count, q] */
+} simplex_batch_branch_t;
+
+int simplex_solve_batch_device_branch(const simplex_batch_device_t *args,
+                                      const simplex_batch_state_t *in /* required: P problems of shape (n, m - 1) */,
+                                      const simplex_batch_state_t *out /* NULL: not kept; count problems of shape (n, m) */,
+                                      const simplex_batch_branch_t *br);
+
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through
  * element strides (a transposed or sliced view is not copied; negative strides are accepted, with

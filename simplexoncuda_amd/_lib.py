@@ -82,6 +82,15 @@ class BatchStateT(ctypes.Structure):
     ]
 
 
+class BatchBranchT(ctypes.Structure):
+    """simplex_batch_branch_t (include/simplex_hip.h); every pointer is a device address."""
+    _fields_ = [
+        ("roots", ctypes.c_int), ("parents", ctypes.c_int), ("depth", ctypes.c_int),
+        ("root", ctypes.c_void_p), ("parent", ctypes.c_void_p), ("var", ctypes.c_void_p), ("coef", ctypes.c_void_p),
+        ("rhs", ctypes.c_void_p),
+    ]
+
+
 class DeviceSolveT(ctypes.Structure):
     """simplex_device_solve_t (include/simplex_hip.h); every pointer is a device address."""
     _fields_ = [
@@ -176,6 +185,8 @@ SIGNATURES = {
     "simplex_solve_batch_device_drop": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.POINTER(BatchStateT),
                                                        ctypes.POINTER(BatchStateT), ctypes.c_int, ctypes.c_int,
                                                        ctypes.c_void_p]),
+    "simplex_solve_batch_device_branch": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.POINTER(BatchStateT),
+                                                         ctypes.POINTER(BatchStateT), ctypes.POINTER(BatchBranchT)]),
     "simplex_solve_device": (ctypes.c_int, [ctypes.POINTER(DeviceSolveT), c_int_p, c_double_p, c_ll_p, c_int_p]),
     "simplex_problem_from_arrays": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "simplex_generate_problem_ex": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,

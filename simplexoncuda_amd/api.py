@@ -438,10 +438,8 @@ def solve_batch_tensors(A, b, c, max_pivots=-1, objective_row=False, finish=True
     return out
 
 
-def _check_state_and_costs(fn, state, c, grown=False):
-    """a BatchState's tensors and the costs that go with it, checked on the host: (B, n, m, device).
-    grown: c belongs to a problem of another number of variables than the state's -- more (new columns) or
-    fewer (dropped ones); the caller tests how many"""
+def _check_state(fn, state):
+    """a BatchState's tensors, checked on the host: (B, n, m, device)"""
     import torch
 
     n, m = state.n, state.m
@@ -455,6 +453,16 @@ def _check_state_and_costs(fn, state, c, grown=False):
             raise ValueError(f"{fn}: state.{name} must be a contiguous {dtype} tensor of shape {shape}")
         if t.device != dev:
             raise ValueError(f"{fn}: the state's tensors must be on one device")
+    return B, n, m, dev
+
+
+def _check_state_and_costs(fn, state, c, grown=False):
+    """a BatchState's tensors and the costs that go with it, checked on the host: (B, n, m, device).
+    grown: c belongs to a problem of another number of variables than the state's -- more (new columns) or
+    fewer (dropped ones); the caller tests how many"""
+    import torch
+
+    B, n, m, dev = _check_state(fn, state)
     if not isinstance(c, torch.Tensor):
         raise TypeError(f"{fn}: c must be a torch.Tensor, not {type(c).__name__}")
     if c.dtype != torch.float64:
@@ -640,6 +648,102 @@ def _edit_batch_state(fn, entry, state, A, b, c, grown, shapes, max_pivots, obje
     out = BatchTensors(*outputs, None, None, new)
     if finish:
         out.evicted = _evicted_count(out.evicted, B)
+    return out
+
+
+def branch_batch_tensors(state, parent, var, coef, rhs, A, b, c, root=None, max_pivots=-1, objective_row=False,
+                         keep_state=True, finish=True):
+    """Branch the problems of a BatchState on the device (simplex_solve_batch_device_branch): C children,
+    any number per parent, each the parent's problem with one more bound row, without a copy of the
+    problem data or of the state per child.
+
+    state holds P parents of shape (n, state.m).  A [R, mA, n], b [R, mA] and c [R, n] are the R root
+    problems, float64 on the state's device, any strides; they are read in place.  Child k continues
+    state problem parent[k] (int32 [C]) on root problem root[k] (int32 [C]; None: parent, which needs
+    R == P) and carries the q bound rows coef[k, t] * x[var[k, t]] <= rhs[k, t] behind the root's rows:
+    var is int32 [C, q], coef and rhs float64 [C, q], all on the state's device (made contiguous if they
+    are not), and state.m == mA + q - 1.  The first q - 1 rows must be the ones parent[k]'s state was
+    solved with -- pass a level's var, coef and rhs on, gathered by parent and with one more column --
+    and the last one is new: x_j <= floor(x*_j) is (j, 1.0, floor), x_j >= ceil(x*_j) is (j, -1.0, -ceil).
+
+    Every child gets what add_rows_batch_tensors gives for one new row on a gathered copy of its parent's
+    state and the explicit grown A and b, bit for bit, with that call's warm and cold starts (a cold
+    child is built from its root's rows and all q bound rows).  A parent or root index outside the
+    state or the roots, a variable outside [0, n), or a parent state that fails the kernel's checks gives
+    that child BAD_STATE, cleared outputs and phase 0 (see resume_batch_tensors); the other children
+    are not affected.
+
+    Returns a BatchTensors of C rows in the shape (n, mA + q).  With keep_state=True its .state is a new
+    BatchState of that shape with rhs=True, which every kept-state call and the next level's branch
+    take; `state` is left untouched.  keep_state=False keeps none (.state is None): the form for strong
+    branching, many candidate bounds per parent probed for max_pivots dual pivots each.  A probe that
+    max_pivots stops inside the dual loop has status PIVOT_CAP and optimal_value NaN; its dual bound --
+    the objective of a dual feasible basis, which the optimum of the child cannot beat -- is
+    objective_row[:, 0] (ask for objective_row=True).  finish as in resume_batch_tensors."""
+    import torch
+
+    fn = "branch_batch_tensors"
+    if not isinstance(state, BatchState):
+        raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
+    P, n, m0, dev = _check_state(fn, state)
+    for name, t, dtype in (("parent", parent, torch.int32), ("var", var, torch.int32), ("coef", coef, torch.float64),
+                           ("rhs", rhs, torch.float64)) + ((("root", root, torch.int32),) if root is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{fn}: {name} must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype != dtype:
+            raise TypeError(f"{fn}: {name} must be {str(dtype).split('.')[-1]}, not {t.dtype}")
+    if parent.dim() != 1:
+        raise ValueError(f"{fn}: parent must be [C], one entry per child; got {tuple(parent.shape)}")
+    C = parent.shape[0]
+    if C >= 2 ** 31:
+        raise ValueError(f"{fn}: too many children for one call")
+    if var.dim() != 2 or var.shape[0] != C or var.shape[1] < 1:
+        raise ValueError(f"{fn}: var must be [{C}, q] with q >= 1; got {tuple(var.shape)}")
+    q = var.shape[1]
+    for name, t in (("coef", coef), ("rhs", rhs)):
+        if tuple(t.shape) != (C, q):
+            raise ValueError(f"{fn}: {name} must be [{C}, {q}], as var is; got {tuple(t.shape)}")
+    if root is not None and tuple(root.shape) != (C,):
+        raise ValueError(f"{fn}: root must be [{C}], one entry per child; got {tuple(root.shape)}")
+    R, mA, nA = _check_device_shapes(fn, A, b, c, batch=True)
+    if nA != n:
+        raise ValueError(f"{fn}: A must be [R, mA, {n}], the state's variables; got {tuple(A.shape)}")
+    if R < 1 or R >= 2 ** 31:
+        raise ValueError(f"{fn}: A, b and c must hold at least one root problem")
+    if root is None and R != P:
+        raise ValueError(f"{fn}: without root the parents are the roots, so A must hold the state's {P} problems; "
+                         f"got {R}")
+    if m0 != mA + q - 1:
+        raise ValueError(f"{fn}: a state of {m0} rows is not A's {mA} rows followed by {q} - 1 bound rows")
+    m = mA + q
+    if n < 1 or mA < 1 or P < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+        raise ValueError(f"{fn}: a problem of {n} variables x {m} constraints is not solved by a resident workgroup")
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
+    if A.device != dev or b.device != dev or c.device != dev:
+        raise ValueError(f"{fn}: A, b and c must be on the state's device, {dev}")
+    for name, t in (("parent", parent), ("var", var), ("coef", coef), ("rhs", rhs), ("root", root)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{fn}: {name} is on {t.device}; it must be on the state's device, {dev}")
+    new = None
+    held = []
+
+    def prepare():
+        nonlocal new
+        lists = [t.contiguous() for t in (parent if root is None else root, parent, var, coef, rhs)]
+        held.extend(lists)
+        br = _lib.BatchBranchT(R, P, q, *(t.data_ptr() for t in lists))
+        if keep_state:
+            new = BatchState.empty(C, n, m, dev)
+            new.rhs = True
+        return "simplex_solve_batch_device_branch", (ctypes.byref(state._struct()),
+                                                     ctypes.byref(new._struct()) if keep_state else None,
+                                                     ctypes.byref(br))
+
+    outputs = _call_batch_entry(dev, C, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare)
+    out = BatchTensors(*outputs, None, None, new)
+    if finish:
+        out.evicted = _evicted_count(out.evicted, C)
     return out
 
 

@@ -27,7 +27,9 @@
 // (simplex_solve_batch_device_rows: a saved state grown by new constraint rows, then the same dual loop),
 // k_batch_solve_cols (simplex_solve_batch_device_cols: a saved state grown by new structural
 // columns, then phase 2) and k_batch_solve_drop (simplex_solve_batch_device_drop: constraint rows or
-// structural columns taken out of a saved state by forced pivots, then the same loops).
+// structural columns taken out of a saved state by forced pivots, then the same loops).  k_batch_solve_branch
+// (simplex_solve_batch_device_branch) is k_batch_solve_rows for the children of a branch: many children per
+// kept parent, the new bound row given as (variable, coefficient, right-hand side), no dense row read.
 // What surrounds the method is written once where that costs no time: every kernel names its static
 // LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
 // entries end with the same epilogue, wg_write_results, which writes a problem's results into the
@@ -1238,6 +1240,131 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a
     }
 }
 
+// wg_build of a child of k_batch_solve_branch: orc_build_phase1 of the composite problem whose rows
+// [0, mA) are the root's at src, read through its strides, and whose row mA + t is the bound row
+// cf[t] x_var[t] <= rh[t]: cf[t] at column var[t], +0.0 elsewhere.  The same copies, the same negation
+// of a row with compare(b_i) < 0 across all its entries, and the same walk of A's faster-varying
+// dimension as wg_build, which stays as it is under the other kernels.  Ends behind a barrier.
+__device__ __forceinline__ void wg_build_branch(const BatchWork &w, const SxSource &src, bool by_col, int mA,
+                                                const int *var, const double *cf, const double *rh) {
+    const int n = w.n, m = w.m, ld = w.ld;
+    const auto rhs_of = [&](int i) { return i < mA ? src.b[(long long)i * src.b_si] : rh[i - mA]; };
+    const auto structural = [&](int i, int j) {
+        const double v = i < mA               ? src.A[(long long)i * src.A_sr + (long long)j * src.A_sc]
+                         : j == var[i - mA] ? cf[i - mA]
+                                            : 0.0;
+        w.T[(size_t)i * ld + 1 + j] = cmp_eps(rhs_of(i), 0.0) < 0 ? -v : v;
+    };
+    if (by_col) {
+        for (int x = threadIdx.x; x < n * m; x += SX_TILE) structural(x / n, x % n);
+    } else {
+        for (int x = threadIdx.x; x < n * m; x += SX_TILE) structural(x % m, x / m);
+    }
+    for (int x = threadIdx.x; x < m * (m + 1); x += SX_TILE) {
+        const int i = x / (m + 1), t = x - i * (m + 1);
+        const double b = rhs_of(i);
+        const double v = t == 0 ? b : (t - 1 == i ? 1.0 : 0.0);
+        w.T[(size_t)i * ld + (t == 0 ? 0 : n + t)] = cmp_eps(b, 0.0) < 0 ? -v : v;
+    }
+    for (int j = threadIdx.x; j < 1 + n + 2 * m; j += SX_TILE) w.d[j] = j <= n + m ? 0.0 : 1.0;
+    for (int i = threadIdx.x; i < m; i += SX_TILE) w.base[i] = n + m + i;
+    __syncthreads();
+}
+
+// simplex_solve_batch_device_branch: k_batch_solve_rows with added = 1 for the children of a branch.
+// Child k of the call's shape (n, m) continues the kept state of problem pk = a.parent[k], shape
+// (n, m - 1), on the problem rk = a.root[k] of the source, which holds a.roots problems of mA = m - q
+// rows (q = a.depth); behind the root's rows come the child's q bound rows cf[t] x_var[t] <= rh[t], of
+// which the first q - 1 are what the parent was solved with and the last one is new.  No dense row
+// exists: the new row's raw entries are rh[q - 1] | cf[q - 1] at column var[q - 1], +0.0 elsewhere | the
+// unit slack, its multipliers are cf[q - 1] where base[i] == var[q - 1] and +0.0 elsewhere, and the
+// chain over the old rows is k_batch_solve_rows's, whole, so every bit is that kernel's on the explicit
+// grown problem.  The cold start builds the composite problem (wg_build_branch).
+// The front is this kernel's own because it indexes the in-state with pk and the source with rk, where
+// WG_STATE_TEST and WG_LOAD_STATE know the one name k; results and out-state are written at k, so the
+// tail and the end are the shared ones.  pk, rk and the q variables are tested before anything is
+// indexed with them, then the in-state as k_batch_solve_rows tests it; a child that fails gets
+// SX_BAD_STATE and cleared outputs.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_branch(BatchBranchArgs a) {
+    WG_KEPT_HEAD(a, sc);
+    const int q = a.depth, mA = m - q, m0 = m - 1, Ns0 = Ns - 1, N10 = Ns0 + m0;  // the in-state's shape
+    WG_KEPT_CARVE(a, );
+    const int cells = m * Ns, cells0 = m0 * Ns0;  // (a working set holds them, so they fit an int)
+    for (;;) {
+        const unsigned k = wg_next(a.counter, sc);
+        if (k >= (unsigned)a.count) return;
+        const int pk = a.parent[k], rk = a.root[k];
+        const int *var = a.var + (size_t)k * (size_t)q;
+        const double *cf = a.coef + (size_t)k * (size_t)q, *rh = a.rhs + (size_t)k * (size_t)q;
+        TwoPhase t{SX_BAD_STATE, false, 0, 0};
+        bool dual = false;  // the problem stands inside the dual loop
+        // the child's own indices, before the in-state or the source is indexed with them
+        int off = 0;
+        for (int j = threadIdx.x; j < q; j += SX_TILE) off |= (unsigned)var[j] >= (unsigned)n;
+        bool good = !__syncthreads_or(off) && (unsigned)pk < (unsigned)a.parents && (unsigned)rk < (unsigned)a.roots;
+        // the in-state's own tests, against its shape: k_batch_solve_rows's, at pk
+        int ph = 0;
+        long long q1 = 0, q2 = 0;
+        if (good) {
+            ph = a.in.phase[pk];
+            q1 = a.in.pivots[2 * (size_t)pk];
+            q2 = a.in.pivots[2 * (size_t)pk + 1];
+            good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
+        }
+        if (good) {
+            const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m0) : (unsigned)(n + m0);
+            const int *base_in = a.in.base + (size_t)pk * (size_t)m0;
+            int bad = 0;
+            for (int i = threadIdx.x; i < m; i += SX_TILE) {
+                const int bi = i < m0 ? base_in[i] : n + i;  // the new row's slack is basic
+                w.base[i] = bi;
+                bad |= i < m0 && (unsigned)bi >= lim;
+            }
+            good = !__syncthreads_or(bad);
+        }
+        if (good) {
+            const SxSource src{a.A + (long long)rk * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)rk * a.b_sb, a.b_si,
+                               a.c + (long long)rk * a.c_sb, a.c_sj};
+            bool cold = ph == 1;
+            if (!cold) {
+                // the parent's rows at the child's odd ld, each ending in +0.0 for the new slack
+                wg_load_T(w, a.in.T + (size_t)pk * (size_t)cells0, Ns0, cells0);
+                for (int i = threadIdx.x; i < m0; i += SX_TILE) w.T[(size_t)i * w.ld + Ns0] = 0.0;
+                const double *d_in = a.in.d + (size_t)pk * (size_t)N10;
+                for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;
+                __syncthreads();
+                WG_DUAL_LOST(cold, w, Ns);  // at the child's width
+            }
+            if (cold) {
+                wg_build_branch(w, src, by_col, mA, var, cf, rh);
+                wg_update_objective(w, N1);
+                t.p1 = t.p2 = 0;
+                t.ph2 = dual = false;
+            } else {
+                const int v = var[q - 1];
+                const double cv = cf[q - 1], rv = rh[q - 1];
+                // the multipliers of the new row, once, in colE (m >= m0 doubles, free by now)
+                for (int i = threadIdx.x; i < m0; i += SX_TILE) w.colE[i] = w.base[i] == v ? cv : 0.0;
+                __syncthreads();
+                double *row = w.T + (size_t)m0 * w.ld;
+                for (int j = threadIdx.x; j < Ns; j += SX_TILE) {
+                    double acc = j == 0 ? rv : j <= n ? (j - 1 == v ? cv : 0.0) : (j - 1 - n == m0 ? 1.0 : 0.0);
+                    for (int i = 0; i < m0; ++i) acc = fma(-w.colE[i], w.T[(size_t)i * w.ld + j], acc);
+                    row[j] = acc;
+                }
+                __syncthreads();  // T is complete
+                t.p1 = q1;
+                t.p2 = 0;
+                t.ph2 = dual = true;
+            }
+            WG_KEPT_TAIL(t, dual);
+        }
+        WG_KEPT_END(t, good, dual);
+        __syncthreads();  // the next problem overwrites the working set and sc.k
+    }
+}
+
 // One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
 template <class Args, void (*KL)(Args), void (*KW)(Args)>
 struct Entry {
@@ -1275,6 +1402,7 @@ using RhsEntry = Entry<BatchRhsArgs, k_batch_solve_rhs<true>, k_batch_solve_rhs<
 using RowsEntry = Entry<BatchRowsArgs, k_batch_solve_rows<true>, k_batch_solve_rows<false>>;
 using ColsEntry = Entry<BatchColsArgs, k_batch_solve_cols<true>, k_batch_solve_cols<false>>;
 using DropEntry = Entry<BatchDropArgs, k_batch_solve_drop<true>, k_batch_solve_drop<false>>;
+using BranchEntry = Entry<BatchBranchArgs, k_batch_solve_branch<true>, k_batch_solve_branch<false>>;
 
 }  // namespace
 
@@ -1287,6 +1415,7 @@ int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes) {
     case BatchEntry::Rows: return RowsEntry::resident(lds, lds_bytes);
     case BatchEntry::Cols: return ColsEntry::resident(lds, lds_bytes);
     case BatchEntry::Drop: return DropEntry::resident(lds, lds_bytes);
+    case BatchEntry::Branch: return BranchEntry::resident(lds, lds_bytes);
     default: return HostEntry::resident(lds, lds_bytes);
     }
 }
@@ -1313,4 +1442,7 @@ void sx_launch_batch_solve(bool lds, const BatchColsArgs &a, int grid, size_t ld
 }
 void sx_launch_batch_solve(bool lds, const BatchDropArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     DropEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+void sx_launch_batch_solve(bool lds, const BatchBranchArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    BranchEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

@@ -484,11 +484,25 @@ struct BatchDropArgs : BatchDevArgs {
     int dropped;      // q >= 1 indices per problem
     const int *idx;   // [count][dropped] device: strictly ascending, in [0, m + q) or [0, n + q)
 };
+// The branch entry (simplex_solve_batch_device_branch): n, m and count are the children's; A, b and c
+// hold `roots` problems of m - depth rows, `in` holds `parents` problems of shape (n, m - 1) and `out`
+// count problems of the children's shape.  Child k continues in-state problem parent[k] on the problem
+// root[k], whose rows are followed by the bound rows coef[k][t] x_var[k][t] <= rhs[k][t], t < depth; the
+// last of them is the new one.
+struct BatchBranchArgs : BatchDevArgs {
+    BatchState in;    // required; dense at the in-state's own strides, indexed by parent[k]
+    BatchState out;   // T null: the state is not kept
+    int roots, parents;
+    int depth;        // q in [1, m): bound rows per child
+    const int *root, *parent;  // [count] device: outside [0, roots) / [0, parents) the child gets SX_BAD_STATE
+    const int *var;            // [count][depth] device, dense: outside [0, n) the child gets SX_BAD_STATE
+    const double *coef, *rhs;  // [count][depth] device, dense
+};
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
-// The eight entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
-enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows, Cols, Drop };
+// The nine entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
+enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows, Cols, Drop, Branch };
 // workgroups of that entry's kernel the current device holds at once with this much dynamic LDS
 int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes);
 // one launch of the entry the argument struct belongs to
@@ -500,3 +514,4 @@ void sx_launch_batch_solve(bool lds, const BatchRhsArgs &a, int grid, size_t lds
 void sx_launch_batch_solve(bool lds, const BatchRowsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchColsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchDropArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchBranchArgs &a, int grid, size_t lds_bytes, hipStream_t s);

@@ -2560,9 +2560,10 @@ struct BatchDevPlan {
 // 1, no more than the slices simplex_batch_device_workspace(n, m, count) counted, which workspace_bytes
 // must cover (-5).  wn x wm (the drop entry): the shape the kernel works in -- class, working set, grid and
 // workspace are that shape's -- where it is not the problem's own, which stays the source's and the
-// outputs'.
+// outputs'.  sm rows x scount problems (the branch entry): what the source holds where that is not the
+// call's m and count, for the source's own check.
 static int batch_device_plan(const simplex_batch_device_t *args, BatchEntry entry, bool own_ok, bool c_only,
-                             BatchDevPlan *p, int wn = 0, int wm = 0) {
+                             BatchDevPlan *p, int wn = 0, int wm = 0, int sm = 0, int scount = 0) {
     p->grid = 0;
     if (args == nullptr || args->count < 0) return -1;
     const int n = args->n, m = args->m, count = args->count;
@@ -2574,7 +2575,8 @@ static int batch_device_plan(const simplex_batch_device_t *args, BatchEntry entr
         return -2;
     if (!c_only) {
         const SxSource src{args->A, args->A_sr, args->A_sc, args->b, args->b_si, args->c, args->c_sj};
-        const int rc = device_source_check(n, m, src, true, count, args->A_sb, args->b_sb, args->c_sb);
+        const int rc = device_source_check(n, sm > 0 ? sm : m, src, true, scount > 0 ? scount : count, args->A_sb,
+                                           args->b_sb, args->c_sb);
         if (rc != 0) return rc;
     } else {
         if (args->c == nullptr) return -2;
@@ -2619,9 +2621,9 @@ static int batch_device_enqueue(const simplex_batch_device_t *args, const BatchD
 // becomes the plan's.
 extern "C++" template <class Args>
 static int batch_device_run(const simplex_batch_device_t *args, BatchEntry entry, bool own_ok, bool c_only, Args a,
-                            int wn = 0, int wm = 0) {
+                            int wn = 0, int wm = 0, int sm = 0, int scount = 0) {
     BatchDevPlan p;
-    const int rc = batch_device_plan(args, entry, own_ok, c_only, &p, wn, wm);
+    const int rc = batch_device_plan(args, entry, own_ok, c_only, &p, wn, wm, sm, scount);
     if (rc != 0 || p.grid == 0) return rc;
     static_cast<BatchDevArgs &>(a) = p.a;
     return batch_device_enqueue(args, p, a);
@@ -2702,6 +2704,32 @@ int simplex_solve_batch_device_drop(const simplex_batch_device_t *args, const si
     return batch_device_run(args, BatchEntry::Drop,
                             idx != nullptr && kept_states_ok(in, out) && !states_share(in, out), false,
                             BatchDropArgs{{}, batch_state(in), batch_state(out), kind, dropped, idx}, n0, m0);
+}
+
+// The branch entry (k_batch_solve_branch): args is the children's shape and number, `in` the kept states
+// of the parents, shape (n, m - 1), and the source holds br->roots problems of m - br->depth rows, so
+// the source's check is made against those and not against count and m.
+int simplex_solve_batch_device_branch(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                      const simplex_batch_state_t *out, const simplex_batch_branch_t *br) {
+    int mA = 0, roots = 0;
+    BatchBranchArgs a{{}, batch_state(in), batch_state(out), 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (br != nullptr) {
+        if (args != nullptr && args->count >= 0 &&
+            (br->depth < 1 || br->depth >= args->m || br->roots < 1 || br->parents < 1))
+            return -3;
+        a.roots = roots = br->roots;
+        a.parents = br->parents;
+        a.depth = br->depth;
+        a.root = br->root;
+        a.parent = br->parent;
+        a.var = br->var;
+        a.coef = br->coef;
+        a.rhs = br->rhs;
+        if (args != nullptr) mA = args->m - br->depth;
+    }
+    const bool own_ok = br != nullptr && br->root != nullptr && br->parent != nullptr && br->var != nullptr &&
+                        br->coef != nullptr && br->rhs != nullptr && kept_states_ok(in, out) && !states_share(in, out);
+    return batch_device_run(args, BatchEntry::Branch, own_ok, false, a, 0, 0, mA, roots);
 }
 
 // The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
