@@ -519,6 +519,70 @@ int simplex_solve_batch_device_branch(const simplex_batch_device_t *args,
                                       const simplex_batch_state_t *out /* NULL: not kept; count problems of shape (n, m) */,
                                       const simplex_batch_branch_t *br);
 
+/* Gomory mixed-integer cuts from kept states: simplex_solve_batch_device_rows whose `cuts` = q new rows are
+ * not given but derived, per problem, from the kept optimum, written out in the caller's variables, and
+ * added in the same launch.  args is the grown shape (n, m) and count as there; `in` has the shape (n, m0),
+ * m0 = m - q, and `out` the grown one.  args->A [count][m0][n] and args->b [count][m0] hold the rows the
+ * in-state was solved with and are only read, through the struct's strides (a batch stride may be 0 only
+ * when count == 1).  The new rows are outputs: cut_A [count][q][n] and cut_b [count][q], each through its
+ * own element strides; they may be rows m0 .. m of the arrays args->A and args->b point into, and nothing
+ * the call writes is read back from memory by it.  eps and compare are macro.h's; every fused operation
+ * below is one fma, nothing else is contracted.  Per problem k:
+ *   state tests -- simplex_solve_batch_device_rows's, against (n, m0).  A problem that fails gets
+ *   SIMPLEX_BAD_STATE, cleared outputs, out->phase 0, cut_row[k][.] = -1 and cut_A, cut_b of +0.0.
+ *   usable -- the state is in phase 2 and that entry's warm test holds (the eps-argmin of d[1 .. 1+n+m0)
+ *   followed by q of +0.0 does not compare below zero): a kept optimum.  Every cut of a problem that is
+ *   not usable is the null row.
+ *   cut t = 0 .. q-1, source row -- row i < m0 is eligible when v = base[i] < n, integer[k][v] != 0, with
+ *   t0 = T[i][0] and f0 = t0 - floor(t0) both f0 >= away and 1.0 - f0 >= away, and no cut t' < t took it.
+ *   Its key is -fmin(f0, 1.0 - f0), that of any other row DBL_MAX.  With row NULL the source row r is the
+ *   eps-argmin of the keys by the reference's tree, and there is no cut when the minimum is DBL_MAX; else
+ *   r = row[k][t] if that lies in [0, m0) and is eligible, and there is no cut otherwise.  cut_row[k][t] = r,
+ *   or -1.
+ *   the null row, for no cut -- cut_A[k][t][j] = +0.0 for all j and cut_b[k][t] = +0.0: 0 x <= 0 is valid, so
+ *   every problem of the call grows to the same shape; simplex_solve_batch_device_drop takes it out again.
+ *   coefficients of source row r over the stored columns jj in [0, n+m0) -- f0 as above, rho = f0 /
+ *   (1.0 - f0), alpha = T[r][1+jj].  g_jj = +0.0 when jj is one of base[0 .. m0) or compare(alpha, 0) == 0;
+ *   else for an integer structural (jj < n, integer[k][jj] != 0), with fj = alpha - floor(alpha),
+ *   g = (fj <= f0) ? fj : rho * (1.0 - fj); else (a continuous structural, or any slack: no integrality of
+ *   A or b is assumed) g = (alpha > 0) ? alpha : rho * (-alpha).  Row r reads x_v + sum alpha_jj v_jj = t0
+ *   with every v >= 0, so sum g_jj v_jj >= f0 holds at every point whose integer variables are integral,
+ *   and the kept optimum (every v_jj = 0) violates it by f0.
+ *   the caller's variables -- the stored slack columns are the caller's slacks s_i = b_i - A_i x, so
+ *   cut_A[k][t][j] starts at -g_j and takes acc = fma(g_{n+i}, A[i][j], acc) for i = 0 .. m0-1 in that
+ *   order, and cut_b[k][t] starts at -f0 and takes acc = fma(g_{n+i}, b[i], acc) in the same order: the row
+ *   cut_A x <= cut_b.  (The negation of +0.0 is -0.0; signed zeros are part of the result.)
+ *   then -- simplex_solve_batch_device_rows(args', in, out, q) on the explicit grown problem whose rows
+ *   m0 .. m are the emitted ones: status, pivots, opt, x, base, objrow, row_width and the out-state are that
+ *   call's bit for bit, and so are its warm and cold decisions.  A cold problem's cuts are null rows.
+ * The out-state is a state of every state entry and of this one for the shape (n, m), so rounds chain: a
+ * later cut whose source row has an earlier cut's slack nonbasic has a non-zero g on it, and substitutes it
+ * through that cut's row, a row of A by then.
+ * Returns, decided before any device is touched and in this order: -1 args NULL or count < 0; -3 a shape
+ * (n, m) of class 0, cuts < 1, cuts >= m, or away not in (0, 0.5] (a NaN is not); 0 for count == 0; -2 cut
+ * NULL, integer, cut_A, cut_b or cut_row NULL, a required output NULL, in NULL or incomplete, out incomplete
+ * or sharing a member pointer with in, A, b or c NULL; -4 a zero stride of A, b or c along a dimension
+ * longer than 1 (the row dimension has length m0), a zero stride of cut_A or cut_b along a dimension longer
+ * than 1, a zero integer_sj with n > 1; -5 the workspace, simplex_batch_device_workspace(n, m, count).  The
+ * call only enqueues two small memsets and one launch on `stream`. */
+typedef struct {
+    int cuts;                        /* q >= 1 */
+    double away;                     /* in (0, 0.5]: a source row needs away <= frac <= 1 - away */
+    const unsigned char *integer;    /* [count][n] through (integer_sb, integer_sj); non-zero: integer variable.
+                                        integer_sb may be 0: one mask for every problem */
+    long long integer_sb, integer_sj;
+    const int *row;                  /* [count][q] dense, or NULL: the kernel chooses */
+    double *cut_A;                   /* out [count][q][n] through (cut_A_sb, cut_A_sr, cut_A_sc) */
+    long long cut_A_sb, cut_A_sr, cut_A_sc;
+    double *cut_b;                   /* out [count][q] through (cut_b_sb, cut_b_si) */
+    long long cut_b_sb, cut_b_si;
+    int *cut_row;                    /* out [count][q] dense: the source row, -1 for the null row */
+} simplex_batch_cut_t;
+
+int simplex_solve_batch_device_cut(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                   const simplex_batch_state_t *out /* NULL: not kept */,
+                                   const simplex_batch_cut_t *cut);
+
 /* ---- one large LP from device arrays: the engine solve without a host copy of A ---- */
 /* twoPhaseMethodEx of one problem held in device memory: A, b and c are read in place through
  * element strides (a transposed or sliced view is not copied; negative strides are accepted, with

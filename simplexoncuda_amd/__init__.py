@@ -14,7 +14,7 @@ from .api import (  # noqa: F401
     set_update_waves, set_verbose, set_virtual_ranks,
     BatchState, BatchTensors, batch_class, batch_counts, resume_batch_tensors, set_batch_budget, solve_batch, status_name,
     solve_batch_tensors, add_rows_batch_tensors, add_cols_batch_tensors,
-    drop_rows_batch_tensors, drop_cols_batch_tensors, branch_batch_tensors,
+    drop_rows_batch_tensors, drop_cols_batch_tensors, branch_batch_tensors, cut_batch_tensors,
     SolveTensors, dev_build_phase1_tensors, solve_tensors,
     twoPhaseMethod, twoPhaseMethodEx)
 from ._lib import LIB_PATH, load  # noqa: F401

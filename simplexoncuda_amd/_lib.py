@@ -91,6 +91,19 @@ class BatchBranchT(ctypes.Structure):
     ]
 
 
+class BatchCutT(ctypes.Structure):
+    """simplex_batch_cut_t (include/simplex_hip.h); every pointer is a device address."""
+    _fields_ = [
+        ("cuts", ctypes.c_int), ("away", ctypes.c_double),
+        ("integer", ctypes.c_void_p), ("integer_sb", ctypes.c_longlong), ("integer_sj", ctypes.c_longlong),
+        ("row", ctypes.c_void_p),
+        ("cut_A", ctypes.c_void_p), ("cut_A_sb", ctypes.c_longlong), ("cut_A_sr", ctypes.c_longlong),
+        ("cut_A_sc", ctypes.c_longlong),
+        ("cut_b", ctypes.c_void_p), ("cut_b_sb", ctypes.c_longlong), ("cut_b_si", ctypes.c_longlong),
+        ("cut_row", ctypes.c_void_p),
+    ]
+
+
 class DeviceSolveT(ctypes.Structure):
     """simplex_device_solve_t (include/simplex_hip.h); every pointer is a device address."""
     _fields_ = [
@@ -187,6 +200,8 @@ SIGNATURES = {
                                                        ctypes.c_void_p]),
     "simplex_solve_batch_device_branch": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.POINTER(BatchStateT),
                                                          ctypes.POINTER(BatchStateT), ctypes.POINTER(BatchBranchT)]),
+    "simplex_solve_batch_device_cut": (ctypes.c_int, [ctypes.POINTER(BatchDeviceT), ctypes.POINTER(BatchStateT),
+                                                      ctypes.POINTER(BatchStateT), ctypes.POINTER(BatchCutT)]),
     "simplex_solve_device": (ctypes.c_int, [ctypes.POINTER(DeviceSolveT), c_int_p, c_double_p, c_ll_p, c_int_p]),
     "simplex_problem_from_arrays": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     "simplex_generate_problem_ex": (P_PROBLEM, [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,

@@ -271,6 +271,7 @@ class BatchTensors:
     n_active: object = None  # int32 [B] after a ragged call
     m_active: object = None  # int32 [B] after a ragged call
     state: object = None     # BatchState after keep_state=True or resume_batch_tensors
+    cut_rows: object = None  # int32 [B, cuts] after cut_batch_tensors: each cut's source row, -1 for a null row
 
     @property
     def reduced_costs(self):
@@ -744,6 +745,103 @@ def branch_batch_tensors(state, parent, var, coef, rhs, A, b, c, root=None, max_
     out = BatchTensors(*outputs, None, None, new)
     if finish:
         out.evicted = _evicted_count(out.evicted, C)
+    return out
+
+
+def cut_batch_tensors(state, A, b, c, integer, cuts=1, away=0.05, rows=None, max_pivots=-1, objective_row=False,
+                      keep_state=True, finish=True):
+    """Cut the kept optima of a BatchState on the device (simplex_solve_batch_device_cut): per problem `cuts`
+    Gomory mixed-integer cuts are read off the kept tableau, written in the caller's variables, and added as
+    add_rows_batch_tensors adds rows, all in one launch and without a host round trip.
+
+    A [B, m, n] and b [B, m] are the grown problems, m = state.m + cuts: their first state.m rows, and
+    c [B, n], must be what the state was solved with, and their last `cuts` rows are OVERWRITTEN with the
+    emitted cuts, in place (no copy of A is made), so A and b may not have a zero stride along a dimension
+    longer than 1.  All three are float64 on the state's device.  integer, torch.bool or torch.uint8 of
+    shape [n] or [B, n] on that device, marks the integer variables (slacks always count as continuous).
+
+    Only a kept optimum is cut: a problem in phase 2 whose objective row is dual feasible.  Its cut t comes
+    from the row, not used by an earlier cut of the call, whose basic variable is integer and whose value's
+    fractional part f0 is nearest to 1/2, provided away <= f0 <= 1 - away (ties within eps by the solver's
+    argmin tree); or from rows[k, t] (int32 [B, cuts]) if that row qualifies.  The cut A_cut x <= b_cut
+    holds for every feasible point whose integer variables are integral and is violated by the kept
+    optimum by f0.  Where there is no such row, and in every problem that is not a kept optimum, the cut
+    is the null row, all +0.0: every problem grows to the same shape, and drop_rows_batch_tensors takes
+    the null rows out again.
+
+    Returns add_rows_batch_tensors' result on the grown problem, bit for bit, plus .cut_rows, int32
+    [B, cuts]: the source row of each cut, -1 for a null row.  With keep_state=True .state is a new
+    BatchState of shape (n, m) with rhs=True, which this call takes again for the next round, as every
+    kept-state call does; `state` is left untouched.  A state that fails the kernel's checks gives that
+    problem BAD_STATE and null rows (see resume_batch_tensors).  finish as there."""
+    import torch
+
+    fn = "cut_batch_tensors"
+    if not isinstance(state, BatchState):
+        raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
+    B, n, m0, dev = _check_state_and_costs(fn, state, c)
+    if not isinstance(cuts, int) or isinstance(cuts, bool) or cuts < 1:
+        raise ValueError(f"{fn}: cuts must be an int >= 1; got {cuts!r}")
+    if not (isinstance(away, float) and 0.0 < away <= 0.5):
+        raise ValueError(f"{fn}: away must be a float in (0, 0.5]; got {away!r}")
+    m = m0 + cuts
+    if _check_device_shapes(fn, A, b, c, batch=True) != (B, m, n):
+        raise ValueError(f"{fn}: A must be [{B}, {m}, {n}], the state's {m0} rows and {cuts} for the cuts; "
+                         f"got {tuple(A.shape)}")
+    if not isinstance(integer, torch.Tensor):
+        raise TypeError(f"{fn}: integer must be a torch.Tensor, not {type(integer).__name__}")
+    if integer.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{fn}: integer must be bool or uint8, not {integer.dtype}")
+    if tuple(integer.shape) not in ((n,), (B, n)):
+        raise ValueError(f"{fn}: integer must be [{n}] or [{B}, {n}]; got {tuple(integer.shape)}")
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor):
+            raise TypeError(f"{fn}: rows must be a torch.Tensor, not {type(rows).__name__}")
+        if rows.dtype != torch.int32:
+            raise TypeError(f"{fn}: rows must be int32, not {rows.dtype}")
+        if tuple(rows.shape) != (B, cuts):
+            raise ValueError(f"{fn}: rows must be [{B}, {cuts}]; got {tuple(rows.shape)}")
+    for name, t in (("A", A), ("b", b)):
+        if any(st == 0 and size > 1 for st, size in zip(t.stride(), t.shape)):
+            raise ValueError(f"{fn}: {name} is written, so it may not have a zero stride along a dimension longer "
+                             f"than 1; got strides {tuple(t.stride())}")
+    if n < 1 or m0 < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+        raise ValueError(f"{fn}: a problem of {n} variables x {m} constraints is not solved by a resident workgroup")
+    if dev.type != "cuda":
+        raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
+    if c.device != dev:
+        raise ValueError(f"{fn}: c is on {c.device}; it must be on the state's device, {dev}")
+    if A.device != dev or b.device != dev:
+        raise ValueError(f"{fn}: A and b must be on the state's device, {dev}")
+    for name, t in (("integer", integer), ("rows", rows)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{fn}: {name} is on {t.device}; it must be on the state's device, {dev}")
+    new = None
+    cut_rows = None
+    held = []
+
+    def prepare():
+        nonlocal new, cut_rows
+        mask = integer.view(torch.uint8) if integer.dtype == torch.bool else integer
+        given = None if rows is None else rows.contiguous()
+        held.extend((mask, given))
+        cut_rows = torch.empty((B, cuts), dtype=torch.int32, device=dev)
+        cut = _lib.BatchCutT(
+            cuts=cuts, away=away, integer=mask.data_ptr(), integer_sb=mask.stride(0) if mask.dim() == 2 else 0,
+            integer_sj=mask.stride(-1), row=None if given is None else given.data_ptr(),
+            cut_A=A.data_ptr() + 8 * m0 * A.stride(1), cut_A_sb=A.stride(0), cut_A_sr=A.stride(1), cut_A_sc=A.stride(2),
+            cut_b=b.data_ptr() + 8 * m0 * b.stride(1), cut_b_sb=b.stride(0), cut_b_si=b.stride(1),
+            cut_row=cut_rows.data_ptr())
+        if keep_state:
+            new = BatchState.empty(B, n, m, dev)
+            new.rhs = True
+        return "simplex_solve_batch_device_cut", (ctypes.byref(state._struct()),
+                                                  ctypes.byref(new._struct()) if keep_state else None, ctypes.byref(cut))
+
+    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare)
+    out = BatchTensors(*outputs, None, None, new, cut_rows)
+    if finish:
+        out.evicted = _evicted_count(out.evicted, B)
     return out
 
 

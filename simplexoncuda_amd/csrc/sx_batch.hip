@@ -29,7 +29,9 @@
 // columns, then phase 2) and k_batch_solve_drop (simplex_solve_batch_device_drop: constraint rows or
 // structural columns taken out of a saved state by forced pivots, then the same loops).  k_batch_solve_branch
 // (simplex_solve_batch_device_branch) is k_batch_solve_rows for the children of a branch: many children per
-// kept parent, the new bound row given as (variable, coefficient, right-hand side), no dense row read.
+// kept parent, the new bound row given as (variable, coefficient, right-hand side), no dense row read;
+// k_batch_solve_cut (simplex_solve_batch_device_cut) is k_batch_solve_rows whose new rows are Gomory
+// mixed-integer cuts that the kernel derives from the kept optimum and writes out for the caller.
 // What surrounds the method is written once where that costs no time: every kernel names its static
 // LDS through one WgScratch and draws its next problem with wg_next, and the two one-shape device
 // entries end with the same epilogue, wg_write_results, which writes a problem's results into the
@@ -1365,6 +1367,189 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_branch(BatchBranchAr
     }
 }
 
+// simplex_solve_batch_device_cut: k_batch_solve_rows whose q = a.cuts new rows are not read but
+// produced: Gomory mixed-integer cuts of the kept optimum, written in the caller's variables into
+// a.cut_A and a.cut_b (the wrapper points them at rows m0 .. m of the caller's grown A and b), then
+// reduced and re-solved exactly as that kernel does with rows it reads.  The front
+// never re-reads from global memory what the launch wrote: an emitted row is produced in the working
+// set -- straight in T[m0 + t][0 .. n], where the raw row of k_batch_solve_rows's chain stands --, is
+// stored from there with plain vector stores, and is consumed from there.  Only rows [0, m0) of A and b
+// are read.
+// Usable: a phase-2 state whose row is dual feasible at the grown width, a kept optimum.  Cut t of a
+// usable problem: the source row is the eps-argmin (wg_argmin) of -min(f0, 1 - f0) over the rows whose
+// basic variable is an integer structural, whose right-hand side has the fractional part f0 in
+// [away, 1 - away] and which no earlier cut of the call took (marks in colE), or the caller's row[k][t]
+// if it is such a row.  Its coefficients g over the stored columns [0, n + m0) go to the pivot-row
+// copy, which first holds the basic columns' marks: a lane reads the mark of the element it then
+// writes.  Then consecutive lanes take consecutive structural columns j (lane n: the right-hand side),
+// start at -g_j (-f0) and add g_{n+i} A[i][j] (b[i]) for i = 0 .. m0 - 1 in that order by fma, the
+// accumulator in a register and g_{n+i} an LDS broadcast.  That is one pass over A per cut: q is the
+// call's, not the compiler's, so the q accumulators of a single pass have no registers to live in.
+// Every other cut is the null row, +0.0 throughout; a cold problem's cuts are all null, so its
+// composite build is wg_build_branch's with +0.0 coefficients and right-hand sides (staged in colE).
+// Then k_batch_solve_rows's chain per new row, the multipliers staged in colE from the raw row before
+// the chain overwrites it, the shared tail and the shared end.
+template <bool LDS>
+__global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cut(BatchCutArgs a) {
+    WG_KEPT_HEAD(a, sc);
+    const int q = a.cuts, m0 = m - q, Ns0 = Ns - q, N10 = Ns0 + m0;  // the in-state's shape
+    WG_KEPT_CARVE(a, );
+    const int cells = m * Ns, cells0 = m0 * Ns0;  // (a working set holds them, so they fit an int)
+    const double away = a.away;
+    for (;;) {
+        const unsigned k = wg_next(a.counter, sc);
+        if (k >= (unsigned)a.count) return;
+        const SxSource src{a.A + (long long)k * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)k * a.b_sb, a.b_si,
+                           a.c + (long long)k * a.c_sb, a.c_sj};
+        const unsigned char *isint = a.integer + (long long)k * a.integer_sb;
+        double *const cA = a.cut_A + (long long)k * a.cut_A_sb, *const cb = a.cut_b + (long long)k * a.cut_b_sb;
+        int *const crow = a.cut_row + (size_t)k * (size_t)q;
+        TwoPhase t{SX_BAD_STATE, false, 0, 0};
+        bool dual = false;  // the problem stands inside the dual loop
+        // the in-state's own range: what is valid only for the grown shape is refused
+        WG_STATE_TEST(
+            bool good, a.in, ph >= 1 && ph <= 3, n, m0, m,
+            {
+                const int bi = i < m0 ? base_in[i] : n + i;  // a new row's slack is basic
+                w.base[i] = bi;
+                bad |= i < m0 && (unsigned)bi >= lim;
+            }, );
+        bool cold = !good || ph == 1;
+        if (!cold) {
+            // the in-state's rows at the grown shape's odd ld
+            wg_load_T(w, a.in.T + (size_t)k * (size_t)cells0, Ns0, cells0);
+            for (int x = threadIdx.x; x < m0 * q; x += SX_TILE) {
+                const int i = x / q;
+                w.T[(size_t)i * w.ld + Ns0 + (x - i * q)] = 0.0;
+            }
+            const double *d_in = a.in.d + (size_t)k * (size_t)N10;
+            for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;
+            __syncthreads();
+            WG_DUAL_LOST(cold, w, Ns);  // at the grown width
+        }
+        if (cold) {
+            // no cut: null rows, and nothing of the source row in cut_row
+            for (int x = threadIdx.x; x < q * (n + 1); x += SX_TILE) {
+                const int tt = x / (n + 1), j = x - tt * (n + 1);
+                if (j < n)
+                    cA[(long long)tt * a.cut_A_sr + (long long)j * a.cut_A_sc] = 0.0;
+                else
+                    cb[(long long)tt * a.cut_b_si] = 0.0;
+            }
+            for (int tt = threadIdx.x; tt < q; tt += SX_TILE) crow[tt] = -1;
+        }
+        if (good) {
+            if (cold) {
+                // the composite build of the m0 rows read and q rows of +0.0
+                for (int tt = threadIdx.x; tt < q; tt += SX_TILE) w.colE[tt] = 0.0;
+                __syncthreads();
+                wg_build_branch(w, src, by_col, m0, reinterpret_cast<const int *>(w.colE), w.colE, w.colE);
+                wg_update_objective(w, N1);
+                t.p1 = t.p2 = 0;
+                t.ph2 = dual = false;
+            } else {
+                const bool usable = ph == 2;
+                for (int i = threadIdx.x; i < m0; i += SX_TILE) w.colE[i] = 0.0;  // no row is taken yet
+                __syncthreads();
+                for (int tt = 0; tt < q; ++tt) {
+                    double *row = w.T + (size_t)(m0 + tt) * w.ld;
+                    // the key of row i; DBL_MAX: not eligible
+                    const auto key = [&](int i) {
+                        const int v = w.base[i];
+                        if (v >= n || w.colE[i] != 0.0 || isint[(long long)v * a.integer_sj] == 0) return DBL_MAX;
+                        const double t0 = w.T[(size_t)i * w.ld], f0 = t0 - floor(t0), f1 = 1.0 - f0;
+                        return f0 >= away && f1 >= away ? -fmin(f0, f1) : DBL_MAX;
+                    };
+                    int r = -1;
+                    if (usable) {
+                        if (a.row == nullptr) {
+                            double kv;
+                            wg_argmin(m0, key, w.parts, sc, kv, r);
+                            if (kv == DBL_MAX || r < 0 || r >= m0) r = -1;
+                        } else {
+                            r = a.row[(size_t)k * (size_t)q + tt];
+                            if (r < 0 || r >= m0 || key(r) == DBL_MAX) r = -1;
+                        }
+                    }
+                    if (r >= 0) {
+                        const double *rowr = w.T + (size_t)r * w.ld;
+                        const double t0 = rowr[0], f0 = t0 - floor(t0), rho = f0 / (1.0 - f0);
+                        // the basic columns' marks, then g over them
+                        for (int jj = threadIdx.x; jj < n + m0; jj += SX_TILE) w.prow[jj] = 0.0;
+                        __syncthreads();
+                        for (int i = threadIdx.x; i < m0; i += SX_TILE) w.prow[w.base[i]] = 1.0;
+                        __syncthreads();
+                        for (int jj = threadIdx.x; jj < n + m0; jj += SX_TILE) {
+                            const double al = rowr[1 + jj];
+                            double g = 0.0;
+                            if (w.prow[jj] == 0.0 && cmp_eps(al, 0.0) != 0) {
+                                if (jj < n && isint[(long long)jj * a.integer_sj] != 0) {
+                                    const double fj = al - floor(al);
+                                    g = fj <= f0 ? fj : rho * (1.0 - fj);
+                                } else {
+                                    g = al > 0.0 ? al : rho * -al;
+                                }
+                            }
+                            w.prow[jj] = g;
+                        }
+                        __syncthreads();
+                        // the caller's variables: lane j < n column j of A, lane n the right-hand side
+                        for (int j = threadIdx.x; j <= n; j += SX_TILE) {
+                            const double *col = j < n ? src.A + (long long)j * src.A_sc : src.b;
+                            const long long step = j < n ? src.A_sr : src.b_si;
+                            double acc = j < n ? -w.prow[j] : -f0;
+                            for (int i = 0; i < m0; ++i) acc = fma(w.prow[n + i], col[(long long)i * step], acc);
+                            if (j < n) {
+                                row[1 + j] = acc;
+                                cA[(long long)tt * a.cut_A_sr + (long long)j * a.cut_A_sc] = acc;
+                            } else {
+                                row[0] = acc;
+                                cb[(long long)tt * a.cut_b_si] = acc;
+                            }
+                        }
+                    } else {
+                        for (int j = threadIdx.x; j <= n; j += SX_TILE) {
+                            row[j] = 0.0;
+                            if (j < n)
+                                cA[(long long)tt * a.cut_A_sr + (long long)j * a.cut_A_sc] = 0.0;
+                            else
+                                cb[(long long)tt * a.cut_b_si] = 0.0;
+                        }
+                    }
+                    for (int i = threadIdx.x; i < m; i += SX_TILE) row[1 + n + i] = i == m0 + tt ? 1.0 : 0.0;
+                    if (threadIdx.x == 0) {
+                        crow[tt] = r;
+                        if (r >= 0) w.colE[r] = 1.0;  // taken
+                    }
+                    __syncthreads();
+                }
+                // k_batch_solve_rows's chain, the raw row read from where it stands
+                for (int r = m0; r < m; ++r) {
+                    double *row = w.T + (size_t)r * w.ld;
+                    // the multipliers of the row, once, in colE, before the chain overwrites the row
+                    for (int i = threadIdx.x; i < m0; i += SX_TILE) {
+                        const int bi = w.base[i];
+                        w.colE[i] = bi < n ? row[1 + bi] : 0.0;
+                    }
+                    __syncthreads();
+                    for (int j = threadIdx.x; j < Ns; j += SX_TILE) {
+                        double acc = row[j];
+                        for (int i = 0; i < m0; ++i) acc = fma(-w.colE[i], w.T[(size_t)i * w.ld + j], acc);
+                        row[j] = acc;
+                    }
+                    __syncthreads();  // colE is rewritten for the next row; T is complete behind the last
+                }
+                t.p1 = q1;
+                t.p2 = 0;
+                t.ph2 = dual = true;
+            }
+            WG_KEPT_TAIL(t, dual);
+        }
+        WG_KEPT_END(t, good, dual);
+        __syncthreads();  // the next problem overwrites the working set and sc.k
+    }
+}
+
 // One entry's kernel pair: the dynamic-LDS attribute is set once per kernel.
 template <class Args, void (*KL)(Args), void (*KW)(Args)>
 struct Entry {
@@ -1403,6 +1588,7 @@ using RowsEntry = Entry<BatchRowsArgs, k_batch_solve_rows<true>, k_batch_solve_r
 using ColsEntry = Entry<BatchColsArgs, k_batch_solve_cols<true>, k_batch_solve_cols<false>>;
 using DropEntry = Entry<BatchDropArgs, k_batch_solve_drop<true>, k_batch_solve_drop<false>>;
 using BranchEntry = Entry<BatchBranchArgs, k_batch_solve_branch<true>, k_batch_solve_branch<false>>;
+using CutEntry = Entry<BatchCutArgs, k_batch_solve_cut<true>, k_batch_solve_cut<false>>;
 
 }  // namespace
 
@@ -1416,6 +1602,7 @@ int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes) {
     case BatchEntry::Cols: return ColsEntry::resident(lds, lds_bytes);
     case BatchEntry::Drop: return DropEntry::resident(lds, lds_bytes);
     case BatchEntry::Branch: return BranchEntry::resident(lds, lds_bytes);
+    case BatchEntry::Cut: return CutEntry::resident(lds, lds_bytes);
     default: return HostEntry::resident(lds, lds_bytes);
     }
 }
@@ -1445,4 +1632,7 @@ void sx_launch_batch_solve(bool lds, const BatchDropArgs &a, int grid, size_t ld
 }
 void sx_launch_batch_solve(bool lds, const BatchBranchArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
     BranchEntry::launch(lds, a, a.count, grid, lds_bytes, s);
+}
+void sx_launch_batch_solve(bool lds, const BatchCutArgs &a, int grid, size_t lds_bytes, hipStream_t s) {
+    CutEntry::launch(lds, a, a.count, grid, lds_bytes, s);
 }

@@ -498,11 +498,29 @@ struct BatchBranchArgs : BatchDevArgs {
     const int *var;            // [count][depth] device, dense: outside [0, n) the child gets SX_BAD_STATE
     const double *coef, *rhs;  // [count][depth] device, dense
 };
+// The cut entry (simplex_solve_batch_device_cut): the rows entry's shapes -- n and m are the grown shape,
+// `in` has the shape (n, m - cuts) -- but the new rows are outputs: A and b hold the m - cuts rows the
+// in-state was solved with, and the kernel writes the cuts it derives to cut_A and cut_b, which may be
+// rows m - cuts .. m of the same arrays.
+struct BatchCutArgs : BatchDevArgs {
+    BatchState in;   // required; dense at the in-state's own strides
+    BatchState out;  // T null: the state is not kept
+    int cuts;        // q in [1, m): cuts per problem
+    double away;     // a source row's fractional part lies in [away, 1 - away]
+    const unsigned char *integer;  // [count][n] through the strides; non-zero: an integer variable
+    long long integer_sb, integer_sj;
+    const int *row;  // [count][cuts] dense, or null: the kernel chooses the source rows
+    double *cut_A;   // out [count][cuts][n]
+    long long cut_A_sb, cut_A_sr, cut_A_sc;
+    double *cut_b;   // out [count][cuts]
+    long long cut_b_sb, cut_b_si;
+    int *cut_row;    // out [count][cuts] dense: the source row, -1 for the null row
+};
 // Bytes in front of the slices in a caller's workspace: the work counter, on a line of its own.
 #define SX_BATCH_DEV_HEADER 256
 
-// The nine entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
-enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows, Cols, Drop, Branch };
+// The ten entries of sx_batch.hip, one kernel pair (LDS, workspace) each.
+enum class BatchEntry { Host, Dev, Rag, St, Rhs, Rows, Cols, Drop, Branch, Cut };
 // workgroups of that entry's kernel the current device holds at once with this much dynamic LDS
 int sx_batch_resident(BatchEntry entry, bool lds, size_t lds_bytes);
 // one launch of the entry the argument struct belongs to
@@ -515,3 +533,4 @@ void sx_launch_batch_solve(bool lds, const BatchRowsArgs &a, int grid, size_t ld
 void sx_launch_batch_solve(bool lds, const BatchColsArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchDropArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 void sx_launch_batch_solve(bool lds, const BatchBranchArgs &a, int grid, size_t lds_bytes, hipStream_t s);
+void sx_launch_batch_solve(bool lds, const BatchCutArgs &a, int grid, size_t lds_bytes, hipStream_t s);

@@ -2561,9 +2561,10 @@ struct BatchDevPlan {
 // must cover (-5).  wn x wm (the drop entry): the shape the kernel works in -- class, working set, grid and
 // workspace are that shape's -- where it is not the problem's own, which stays the source's and the
 // outputs'.  sm rows x scount problems (the branch entry): what the source holds where that is not the
-// call's m and count, for the source's own check.
+// call's m and count, for the source's own check.  own_rc (the cut entry): the code the entry's own
+// strides earn, returned behind the source's own codes and in front of the workspace's.
 static int batch_device_plan(const simplex_batch_device_t *args, BatchEntry entry, bool own_ok, bool c_only,
-                             BatchDevPlan *p, int wn = 0, int wm = 0, int sm = 0, int scount = 0) {
+                             BatchDevPlan *p, int wn = 0, int wm = 0, int sm = 0, int scount = 0, int own_rc = 0) {
     p->grid = 0;
     if (args == nullptr || args->count < 0) return -1;
     const int n = args->n, m = args->m, count = args->count;
@@ -2582,6 +2583,7 @@ static int batch_device_plan(const simplex_batch_device_t *args, BatchEntry entr
         if (args->c == nullptr) return -2;
         if ((count > 1 && args->c_sb == 0) || (n > 1 && args->c_sj == 0)) return -4;
     }
+    if (own_rc != 0) return own_rc;
     if (args->workspace == nullptr || reinterpret_cast<uintptr_t>(args->workspace) % 16 != 0 ||
         args->workspace_bytes < SX_BATCH_DEV_HEADER)
         return -5;
@@ -2621,9 +2623,9 @@ static int batch_device_enqueue(const simplex_batch_device_t *args, const BatchD
 // becomes the plan's.
 extern "C++" template <class Args>
 static int batch_device_run(const simplex_batch_device_t *args, BatchEntry entry, bool own_ok, bool c_only, Args a,
-                            int wn = 0, int wm = 0, int sm = 0, int scount = 0) {
+                            int wn = 0, int wm = 0, int sm = 0, int scount = 0, int own_rc = 0) {
     BatchDevPlan p;
-    const int rc = batch_device_plan(args, entry, own_ok, c_only, &p, wn, wm, sm, scount);
+    const int rc = batch_device_plan(args, entry, own_ok, c_only, &p, wn, wm, sm, scount, own_rc);
     if (rc != 0 || p.grid == 0) return rc;
     static_cast<BatchDevArgs &>(a) = p.a;
     return batch_device_enqueue(args, p, a);
@@ -2730,6 +2732,45 @@ int simplex_solve_batch_device_branch(const simplex_batch_device_t *args, const 
     const bool own_ok = br != nullptr && br->root != nullptr && br->parent != nullptr && br->var != nullptr &&
                         br->coef != nullptr && br->rhs != nullptr && kept_states_ok(in, out) && !states_share(in, out);
     return batch_device_run(args, BatchEntry::Branch, own_ok, false, a, 0, 0, mA, roots);
+}
+
+// The cut entry (k_batch_solve_cut): args is the grown shape, `in` the kept state of its first m - cuts
+// rows, and the source holds those rows alone -- rows m - cuts .. m are what the kernel writes, through
+// cut_A and cut_b -- so the source's check is made against m - cuts rows.  The outputs' strides are the
+// entry's own -4: written elements must not alias.
+int simplex_solve_batch_device_cut(const simplex_batch_device_t *args, const simplex_batch_state_t *in,
+                                   const simplex_batch_state_t *out, const simplex_batch_cut_t *cut) {
+    int m0 = 0, own_rc = 0;
+    BatchCutArgs a{{}, batch_state(in), batch_state(out), 0, 0.0, nullptr, 0, 0, nullptr, nullptr, 0, 0, 0, nullptr, 0, 0,
+                   nullptr};
+    if (cut != nullptr) {
+        if (args != nullptr && args->count >= 0) {
+            // (a NaN fails the range test)
+            if (cut->cuts < 1 || cut->cuts >= args->m || !(cut->away > 0.0 && cut->away <= 0.5)) return -3;
+            m0 = args->m - cut->cuts;
+            const bool many = args->count > 1, wide = args->n > 1, rows = cut->cuts > 1;
+            if ((many && (cut->cut_A_sb == 0 || cut->cut_b_sb == 0)) || (rows && (cut->cut_A_sr == 0 || cut->cut_b_si == 0)) ||
+                (wide && (cut->cut_A_sc == 0 || cut->integer_sj == 0)))
+                own_rc = -4;
+        }
+        a.cuts = cut->cuts;
+        a.away = cut->away;
+        a.integer = cut->integer;
+        a.integer_sb = cut->integer_sb;
+        a.integer_sj = cut->integer_sj;
+        a.row = cut->row;
+        a.cut_A = cut->cut_A;
+        a.cut_A_sb = cut->cut_A_sb;
+        a.cut_A_sr = cut->cut_A_sr;
+        a.cut_A_sc = cut->cut_A_sc;
+        a.cut_b = cut->cut_b;
+        a.cut_b_sb = cut->cut_b_sb;
+        a.cut_b_si = cut->cut_b_si;
+        a.cut_row = cut->cut_row;
+    }
+    const bool own_ok = cut != nullptr && cut->integer != nullptr && cut->cut_A != nullptr && cut->cut_b != nullptr &&
+                        cut->cut_row != nullptr && kept_states_ok(in, out) && !states_share(in, out);
+    return batch_device_run(args, BatchEntry::Cut, own_ok, false, a, 0, 0, m0, 0, own_rc);
 }
 
 // The ragged entry: args->n x args->m is the envelope, problem k its n_k[k] x m_k[k] leading block.
