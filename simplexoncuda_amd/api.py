@@ -573,7 +573,7 @@ def add_rows_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, f
         if n < 1 or m0 < 1 or batch_class(n, m) == 0:  # (host arithmetic)
             raise ValueError(f"add_rows_batch_tensors: a problem of {n} variables x {m} constraints is not solved by "
                              "a resident workgroup")
-        return n, m, (m - m0,), None
+        return B, n, m, lambda: ((m - m0,), None), None
 
     return _edit_batch_state("add_rows_batch_tensors", "simplex_solve_batch_device_rows", state, A, b, c, False, shapes,
                              max_pivots, objective_row, finish)
@@ -609,46 +609,57 @@ def add_cols_batch_tensors(state, A, b, c, max_pivots=-1, objective_row=False, f
         if n0 < 1 or m < 1 or batch_class(n, m) == 0:  # (host arithmetic)
             raise ValueError(f"add_cols_batch_tensors: a problem of {n} variables x {m} constraints is not solved by "
                              "a resident workgroup")
-        return n, m, (n - n0,), None
+        return B, n, m, lambda: ((n - n0,), None), None
 
     return _edit_batch_state("add_cols_batch_tensors", "simplex_solve_batch_device_cols", state, A, b, c, True, shapes,
                              max_pivots, objective_row, finish)
 
 
-def _edit_batch_state(fn, entry, state, A, b, c, grown, shapes, max_pivots, objective_row, finish, idx=None, what=None):
-    """What add_rows_, add_cols_ and the drop_*_batch_tensors share: a kept state edited into a new one of
-    another shape (simplex_solve_batch_device_rows, _cols, _drop).  shapes(B, n0, m0), called with the
-    state's checked shape, is the caller's own shape arithmetic with its errors: it returns the call's n
-    and m, the entry's arguments behind the two states, and the shape the kernel works in where that is
-    not (n, m).  idx: the drop entry's index tensor, `what` in messages; it is the entry's last argument."""
+def _edit_batch_state(fn, entry, state, A, b, c, grown, shapes, max_pivots, objective_row, finish, placed=(),
+                      keep_state=True):
+    """What add_rows_, add_cols_, the drop_*_, branch_ and cut_batch_tensors share: a kept state edited into
+    a new one of another shape (simplex_solve_batch_device_rows, _cols, _drop, _branch, _cut).
+    shapes(B, n0, m0), called with the state's checked shape, is the caller's own argument checks and shape
+    arithmetic with their errors: it returns the call's problem count (branch: the children, not the state's
+    parents), its n and m, `tail`, and the shape the kernel works in where that is not (n, m).  tail() is
+    called once the outputs exist and before the new state does: it makes the caller's own allocations and
+    returns the entry's arguments behind the two states and whatever they point to, which is held until the
+    call has been made.
+    grown: _check_state_and_costs'; None: the source is not the state's problems (branch's roots), so c is
+    the caller's to check and is placed with A and b.  placed: (name, tensor or None) pairs that must be on
+    the state's device.  keep_state=False: no new state is written and .state is None."""
     if not isinstance(state, BatchState):
         raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
-    B, n0, m0, dev = _check_state_and_costs(fn, state, c, grown=grown)
-    n, m, tail, work_shape = shapes(B, n0, m0)
+    B, n0, m0, dev = _check_state(fn, state) if grown is None else _check_state_and_costs(fn, state, c, grown=grown)
+    count, n, m, tail, work_shape = shapes(B, n0, m0)
     if dev.type != "cuda":
         raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
-    if c.device != dev:
-        raise ValueError(f"{fn}: c is on {c.device}; it must be on the state's device, {dev}")
-    if A.device != dev or b.device != dev:
-        raise ValueError(f"{fn}: A and b must be on the state's device, {dev}")
-    if idx is not None and idx.device != dev:
-        raise ValueError(f"{fn}: {what} is on {idx.device}; it must be on the state's device, {dev}")
-    new = None
+    if grown is None:
+        if A.device != dev or b.device != dev or c.device != dev:
+            raise ValueError(f"{fn}: A, b and c must be on the state's device, {dev}")
+    else:
+        if c.device != dev:
+            raise ValueError(f"{fn}: c is on {c.device}; it must be on the state's device, {dev}")
+        if A.device != dev or b.device != dev:
+            raise ValueError(f"{fn}: A and b must be on the state's device, {dev}")
+    for name, t in placed:
+        if t is not None and t.device != dev:
+            raise ValueError(f"{fn}: {name} is on {t.device}; it must be on the state's device, {dev}")
+    new = held = None
 
     def prepare():
-        nonlocal new, idx
-        if idx is not None:
-            idx = idx.contiguous()
-        new = BatchState.empty(B, n, m, dev)
-        new.rhs = True
-        return entry, (ctypes.byref(state._struct()), ctypes.byref(new._struct())) + tail + (
-            () if idx is None else (idx.data_ptr(),))
+        nonlocal new, held
+        extra, held = tail()
+        if keep_state:
+            new = BatchState.empty(count, n, m, dev)
+            new.rhs = True
+        return entry, (ctypes.byref(state._struct()), ctypes.byref(new._struct()) if keep_state else None) + extra
 
-    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare,
+    outputs = _call_batch_entry(dev, count, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare,
                                 work_shape=work_shape)
     out = BatchTensors(*outputs, None, None, new)
     if finish:
-        out.evicted = _evicted_count(out.evicted, B)
+        out.evicted = _evicted_count(out.evicted, count)
     return out
 
 
@@ -684,68 +695,50 @@ def branch_batch_tensors(state, parent, var, coef, rhs, A, b, c, root=None, max_
     import torch
 
     fn = "branch_batch_tensors"
-    if not isinstance(state, BatchState):
-        raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
-    P, n, m0, dev = _check_state(fn, state)
-    for name, t, dtype in (("parent", parent, torch.int32), ("var", var, torch.int32), ("coef", coef, torch.float64),
-                           ("rhs", rhs, torch.float64)) + ((("root", root, torch.int32),) if root is not None else ()):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{fn}: {name} must be a torch.Tensor, not {type(t).__name__}")
-        if t.dtype != dtype:
-            raise TypeError(f"{fn}: {name} must be {str(dtype).split('.')[-1]}, not {t.dtype}")
-    if parent.dim() != 1:
-        raise ValueError(f"{fn}: parent must be [C], one entry per child; got {tuple(parent.shape)}")
-    C = parent.shape[0]
-    if C >= 2 ** 31:
-        raise ValueError(f"{fn}: too many children for one call")
-    if var.dim() != 2 or var.shape[0] != C or var.shape[1] < 1:
-        raise ValueError(f"{fn}: var must be [{C}, q] with q >= 1; got {tuple(var.shape)}")
-    q = var.shape[1]
-    for name, t in (("coef", coef), ("rhs", rhs)):
-        if tuple(t.shape) != (C, q):
-            raise ValueError(f"{fn}: {name} must be [{C}, {q}], as var is; got {tuple(t.shape)}")
-    if root is not None and tuple(root.shape) != (C,):
-        raise ValueError(f"{fn}: root must be [{C}], one entry per child; got {tuple(root.shape)}")
-    R, mA, nA = _check_device_shapes(fn, A, b, c, batch=True)
-    if nA != n:
-        raise ValueError(f"{fn}: A must be [R, mA, {n}], the state's variables; got {tuple(A.shape)}")
-    if R < 1 or R >= 2 ** 31:
-        raise ValueError(f"{fn}: A, b and c must hold at least one root problem")
-    if root is None and R != P:
-        raise ValueError(f"{fn}: without root the parents are the roots, so A must hold the state's {P} problems; "
-                         f"got {R}")
-    if m0 != mA + q - 1:
-        raise ValueError(f"{fn}: a state of {m0} rows is not A's {mA} rows followed by {q} - 1 bound rows")
-    m = mA + q
-    if n < 1 or mA < 1 or P < 1 or batch_class(n, m) == 0:  # (host arithmetic)
-        raise ValueError(f"{fn}: a problem of {n} variables x {m} constraints is not solved by a resident workgroup")
-    if dev.type != "cuda":
-        raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
-    if A.device != dev or b.device != dev or c.device != dev:
-        raise ValueError(f"{fn}: A, b and c must be on the state's device, {dev}")
-    for name, t in (("parent", parent), ("var", var), ("coef", coef), ("rhs", rhs), ("root", root)):
-        if t is not None and t.device != dev:
-            raise ValueError(f"{fn}: {name} is on {t.device}; it must be on the state's device, {dev}")
-    new = None
-    held = []
 
-    def prepare():
-        nonlocal new
-        lists = [t.contiguous() for t in (parent if root is None else root, parent, var, coef, rhs)]
-        held.extend(lists)
-        br = _lib.BatchBranchT(R, P, q, *(t.data_ptr() for t in lists))
-        if keep_state:
-            new = BatchState.empty(C, n, m, dev)
-            new.rhs = True
-        return "simplex_solve_batch_device_branch", (ctypes.byref(state._struct()),
-                                                     ctypes.byref(new._struct()) if keep_state else None,
-                                                     ctypes.byref(br))
+    def shapes(P, n, m0):
+        for name, t, dtype in (("parent", parent, torch.int32), ("var", var, torch.int32), ("coef", coef, torch.float64),
+                               ("rhs", rhs, torch.float64)) + ((("root", root, torch.int32),) if root is not None else ()):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{fn}: {name} must be a torch.Tensor, not {type(t).__name__}")
+            if t.dtype != dtype:
+                raise TypeError(f"{fn}: {name} must be {str(dtype).split('.')[-1]}, not {t.dtype}")
+        if parent.dim() != 1:
+            raise ValueError(f"{fn}: parent must be [C], one entry per child; got {tuple(parent.shape)}")
+        C = parent.shape[0]
+        if C >= 2 ** 31:
+            raise ValueError(f"{fn}: too many children for one call")
+        if var.dim() != 2 or var.shape[0] != C or var.shape[1] < 1:
+            raise ValueError(f"{fn}: var must be [{C}, q] with q >= 1; got {tuple(var.shape)}")
+        q = var.shape[1]
+        for name, t in (("coef", coef), ("rhs", rhs)):
+            if tuple(t.shape) != (C, q):
+                raise ValueError(f"{fn}: {name} must be [{C}, {q}], as var is; got {tuple(t.shape)}")
+        if root is not None and tuple(root.shape) != (C,):
+            raise ValueError(f"{fn}: root must be [{C}], one entry per child; got {tuple(root.shape)}")
+        R, mA, nA = _check_device_shapes(fn, A, b, c, batch=True)
+        if nA != n:
+            raise ValueError(f"{fn}: A must be [R, mA, {n}], the state's variables; got {tuple(A.shape)}")
+        if R < 1 or R >= 2 ** 31:
+            raise ValueError(f"{fn}: A, b and c must hold at least one root problem")
+        if root is None and R != P:
+            raise ValueError(f"{fn}: without root the parents are the roots, so A must hold the state's {P} problems; "
+                             f"got {R}")
+        if m0 != mA + q - 1:
+            raise ValueError(f"{fn}: a state of {m0} rows is not A's {mA} rows followed by {q} - 1 bound rows")
+        m = mA + q
+        if n < 1 or mA < 1 or P < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+            raise ValueError(f"{fn}: a problem of {n} variables x {m} constraints is not solved by a resident workgroup")
 
-    outputs = _call_batch_entry(dev, C, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare)
-    out = BatchTensors(*outputs, None, None, new)
-    if finish:
-        out.evicted = _evicted_count(out.evicted, C)
-    return out
+        def tail():
+            lists = [t.contiguous() for t in (parent if root is None else root, parent, var, coef, rhs)]
+            return (ctypes.byref(_lib.BatchBranchT(R, P, q, *(t.data_ptr() for t in lists))),), lists
+
+        return C, n, m, tail, None
+
+    return _edit_batch_state(fn, "simplex_solve_batch_device_branch", state, A, b, c, None, shapes, max_pivots,
+                             objective_row, finish, keep_state=keep_state,
+                             placed=(("parent", parent), ("var", var), ("coef", coef), ("rhs", rhs), ("root", root)))
 
 
 def cut_batch_tensors(state, A, b, c, integer, cuts=1, away=0.05, rows=None, max_pivots=-1, objective_row=False,
@@ -777,71 +770,54 @@ def cut_batch_tensors(state, A, b, c, integer, cuts=1, away=0.05, rows=None, max
     import torch
 
     fn = "cut_batch_tensors"
-    if not isinstance(state, BatchState):
-        raise TypeError(f"{fn}: state must be a BatchState, not {type(state).__name__}")
-    B, n, m0, dev = _check_state_and_costs(fn, state, c)
-    if not isinstance(cuts, int) or isinstance(cuts, bool) or cuts < 1:
-        raise ValueError(f"{fn}: cuts must be an int >= 1; got {cuts!r}")
-    if not (isinstance(away, float) and 0.0 < away <= 0.5):
-        raise ValueError(f"{fn}: away must be a float in (0, 0.5]; got {away!r}")
-    m = m0 + cuts
-    if _check_device_shapes(fn, A, b, c, batch=True) != (B, m, n):
-        raise ValueError(f"{fn}: A must be [{B}, {m}, {n}], the state's {m0} rows and {cuts} for the cuts; "
-                         f"got {tuple(A.shape)}")
-    if not isinstance(integer, torch.Tensor):
-        raise TypeError(f"{fn}: integer must be a torch.Tensor, not {type(integer).__name__}")
-    if integer.dtype not in (torch.bool, torch.uint8):
-        raise TypeError(f"{fn}: integer must be bool or uint8, not {integer.dtype}")
-    if tuple(integer.shape) not in ((n,), (B, n)):
-        raise ValueError(f"{fn}: integer must be [{n}] or [{B}, {n}]; got {tuple(integer.shape)}")
-    if rows is not None:
-        if not isinstance(rows, torch.Tensor):
-            raise TypeError(f"{fn}: rows must be a torch.Tensor, not {type(rows).__name__}")
-        if rows.dtype != torch.int32:
-            raise TypeError(f"{fn}: rows must be int32, not {rows.dtype}")
-        if tuple(rows.shape) != (B, cuts):
-            raise ValueError(f"{fn}: rows must be [{B}, {cuts}]; got {tuple(rows.shape)}")
-    for name, t in (("A", A), ("b", b)):
-        if any(st == 0 and size > 1 for st, size in zip(t.stride(), t.shape)):
-            raise ValueError(f"{fn}: {name} is written, so it may not have a zero stride along a dimension longer "
-                             f"than 1; got strides {tuple(t.stride())}")
-    if n < 1 or m0 < 1 or batch_class(n, m) == 0:  # (host arithmetic)
-        raise ValueError(f"{fn}: a problem of {n} variables x {m} constraints is not solved by a resident workgroup")
-    if dev.type != "cuda":
-        raise ValueError(f"{fn}: the state is on {dev}; it must be on a GPU")
-    if c.device != dev:
-        raise ValueError(f"{fn}: c is on {c.device}; it must be on the state's device, {dev}")
-    if A.device != dev or b.device != dev:
-        raise ValueError(f"{fn}: A and b must be on the state's device, {dev}")
-    for name, t in (("integer", integer), ("rows", rows)):
-        if t is not None and t.device != dev:
-            raise ValueError(f"{fn}: {name} is on {t.device}; it must be on the state's device, {dev}")
-    new = None
     cut_rows = None
-    held = []
 
-    def prepare():
-        nonlocal new, cut_rows
-        mask = integer.view(torch.uint8) if integer.dtype == torch.bool else integer
-        given = None if rows is None else rows.contiguous()
-        held.extend((mask, given))
-        cut_rows = torch.empty((B, cuts), dtype=torch.int32, device=dev)
-        cut = _lib.BatchCutT(
-            cuts=cuts, away=away, integer=mask.data_ptr(), integer_sb=mask.stride(0) if mask.dim() == 2 else 0,
-            integer_sj=mask.stride(-1), row=None if given is None else given.data_ptr(),
-            cut_A=A.data_ptr() + 8 * m0 * A.stride(1), cut_A_sb=A.stride(0), cut_A_sr=A.stride(1), cut_A_sc=A.stride(2),
-            cut_b=b.data_ptr() + 8 * m0 * b.stride(1), cut_b_sb=b.stride(0), cut_b_si=b.stride(1),
-            cut_row=cut_rows.data_ptr())
-        if keep_state:
-            new = BatchState.empty(B, n, m, dev)
-            new.rhs = True
-        return "simplex_solve_batch_device_cut", (ctypes.byref(state._struct()),
-                                                  ctypes.byref(new._struct()) if keep_state else None, ctypes.byref(cut))
+    def shapes(B, n, m0):
+        if not isinstance(cuts, int) or isinstance(cuts, bool) or cuts < 1:
+            raise ValueError(f"{fn}: cuts must be an int >= 1; got {cuts!r}")
+        if not (isinstance(away, float) and 0.0 < away <= 0.5):
+            raise ValueError(f"{fn}: away must be a float in (0, 0.5]; got {away!r}")
+        m = m0 + cuts
+        if _check_device_shapes(fn, A, b, c, batch=True) != (B, m, n):
+            raise ValueError(f"{fn}: A must be [{B}, {m}, {n}], the state's {m0} rows and {cuts} for the cuts; "
+                             f"got {tuple(A.shape)}")
+        if not isinstance(integer, torch.Tensor):
+            raise TypeError(f"{fn}: integer must be a torch.Tensor, not {type(integer).__name__}")
+        if integer.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{fn}: integer must be bool or uint8, not {integer.dtype}")
+        if tuple(integer.shape) not in ((n,), (B, n)):
+            raise ValueError(f"{fn}: integer must be [{n}] or [{B}, {n}]; got {tuple(integer.shape)}")
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor):
+                raise TypeError(f"{fn}: rows must be a torch.Tensor, not {type(rows).__name__}")
+            if rows.dtype != torch.int32:
+                raise TypeError(f"{fn}: rows must be int32, not {rows.dtype}")
+            if tuple(rows.shape) != (B, cuts):
+                raise ValueError(f"{fn}: rows must be [{B}, {cuts}]; got {tuple(rows.shape)}")
+        for name, t in (("A", A), ("b", b)):
+            if any(st == 0 and size > 1 for st, size in zip(t.stride(), t.shape)):
+                raise ValueError(f"{fn}: {name} is written, so it may not have a zero stride along a dimension longer "
+                                 f"than 1; got strides {tuple(t.stride())}")
+        if n < 1 or m0 < 1 or batch_class(n, m) == 0:  # (host arithmetic)
+            raise ValueError(f"{fn}: a problem of {n} variables x {m} constraints is not solved by a resident workgroup")
 
-    outputs = _call_batch_entry(dev, B, n, m, max_pivots, objective_row, _source_fields(A, b, c), prepare)
-    out = BatchTensors(*outputs, None, None, new, cut_rows)
-    if finish:
-        out.evicted = _evicted_count(out.evicted, B)
+        def tail():
+            nonlocal cut_rows
+            mask = integer.view(torch.uint8) if integer.dtype == torch.bool else integer
+            given = None if rows is None else rows.contiguous()
+            cut_rows = torch.empty((B, cuts), dtype=torch.int32, device=state.T.device)
+            return (ctypes.byref(_lib.BatchCutT(
+                cuts=cuts, away=away, integer=mask.data_ptr(), integer_sb=mask.stride(0) if mask.dim() == 2 else 0,
+                integer_sj=mask.stride(-1), row=None if given is None else given.data_ptr(),
+                cut_A=A.data_ptr() + 8 * m0 * A.stride(1), cut_A_sb=A.stride(0), cut_A_sr=A.stride(1),
+                cut_A_sc=A.stride(2), cut_b=b.data_ptr() + 8 * m0 * b.stride(1), cut_b_sb=b.stride(0),
+                cut_b_si=b.stride(1), cut_row=cut_rows.data_ptr())),), (mask, given)
+
+        return B, n, m, tail, None
+
+    out = _edit_batch_state(fn, "simplex_solve_batch_device_cut", state, A, b, c, False, shapes, max_pivots,
+                            objective_row, finish, keep_state=keep_state, placed=(("integer", integer), ("rows", rows)))
+    out.cut_rows = cut_rows
     return out
 
 
@@ -866,10 +842,15 @@ def _drop_batch_tensors(fn, kind, state, idx, A, b, c, max_pivots, objective_row
             raise ValueError(f"{fn}: A must be [{B}, {m}, {n}], the reduced problem; got {tuple(A.shape)}")
         if n0 < 1 or m0 < 1 or batch_class(n0, m0) == 0:  # (host arithmetic)
             raise ValueError(f"{fn}: no resident state exists for {n0} variables x {m0} constraints")
-        return n, m, (kind, q), (n0, m0)
+
+        def tail():
+            ix = idx.contiguous()
+            return (kind, q, ix.data_ptr()), ix
+
+        return B, n, m, tail, (n0, m0)
 
     return _edit_batch_state(fn, "simplex_solve_batch_device_drop", state, A, b, c, True, shapes, max_pivots,
-                             objective_row, finish, idx=idx, what=what)
+                             objective_row, finish, placed=((what, idx),))
 
 
 def drop_rows_batch_tensors(state, rows, A, b, c, max_pivots=-1, objective_row=False, finish=True):

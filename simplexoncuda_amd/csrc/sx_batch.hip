@@ -490,12 +490,14 @@ __device__ __forceinline__ void wg_load_T(const BatchWork &wk, const double *T_i
         }                                                                                                           \
     } while (0)
 
-// What the kernels on a kept state share (k_batch_solve_st, _rhs, _rows, _cols, _drop), written once;
-// each kernel keeps its own front: how the in-state is embedded into the working set and what makes the
-// tableau canonical again.  All but the dense load (wg_load_T) are macros, expanded in the kernel's
-// body, which declares a, sc, w, src, k and the names of the head: as functions, and even with the
-// head's declarations in another order, they leave the kernels' instructions other than they were
-// (DESIGN.md §10.8).
+// What the kernels on a kept state share (k_batch_solve_st, _rhs, _rows, _cols, _drop, _branch, _cut),
+// written once; each kernel keeps its own front: how the in-state is embedded into the working set and
+// what makes the tableau canonical again -- of which the three that grow the state by rows (_rows,
+// _branch, _cut) share the embedding and the reduction of a new row (WG_GROWN_ROW, WG_LOAD_GROWN,
+// WG_REDUCE_ROW) and keep where a new row comes from.  All but the dense load (wg_load_T) are macros,
+// expanded in the kernel's body, which declares a, sc, w, src, k and the names of the head: as
+// functions, and even with the head's declarations in another order, they leave the kernels'
+// instructions other than they were.
 //
 // WG_KEPT_HEAD -- the kernel's head, in two parts with the in-state's shape between them: the static
 // and dynamic LDS, the working set W and the call's shape with its widths; then (WG_KEPT_CARVE) the
@@ -512,31 +514,84 @@ __device__ __forceinline__ void wg_load_T(const BatchWork &wk, const double *T_i
     const long long budget = (a).budget > 0 ? (a).budget : sx_batch_default_budget(n, m);                 \
     const bool by_col = ((a).A_sc < 0 ? -(a).A_sc : (a).A_sc) <= ((a).A_sr < 0 ? -(a).A_sr : (a).A_sr)
 
-// WG_STATE_TEST -- the in-state of problem k, shape (n0, m0), tested before anything is indexed with
-// it: the phase (PH_OK, an expression in ph), both pivot counts >= 0, then the basis, which indexes d
-// (and, through the alias, T), so phase 2 knows no artificial variable.  Declares ph, q1, q2; the
-// result is the kernel's `good`, which GOOD declares (`bool good`) or names (k_batch_solve_st's).
-// The basis is loaded on the way: ROW is the statement for row i < rows, which reads base_in[i], stores
-// the working set's entry and ors an entry outside [0, lim) into bad (WG_BASE_ROW: the entry as it
-// is); MORE is a further statement that ors into bad.  Ends behind a barrier.
+// WG_STATE_TEST -- the in-state of problem sk (the kernel's k, but for k_batch_solve_branch's parent),
+// shape (n0, m0), tested before anything is indexed with it: the phase (PH_OK, an expression in ph),
+// both pivot counts >= 0, then the basis, which indexes d (and, through the alias, T), so phase 2 knows
+// no artificial variable.  Declares ph, q1, q2; the result is the kernel's `good`, which GOOD declares
+// (`bool good`) or names (k_batch_solve_st's).  The basis is loaded on the way: ROW is the statement for
+// row i < rows, which reads base_in[i], stores the working set's entry and ors an entry outside
+// [0, lim) into bad (WG_BASE_ROW: the entry as it is; WG_GROWN_ROW: the in-state's m0 entries tested
+// against its own range -- what is valid only for the grown shape is refused --, behind them the new
+// rows' slacks, which are basic); MORE is a further statement that ors into bad.  Ends behind a barrier.
 #define WG_BASE_ROW(wk)                 \
     {                                   \
         const int bi = base_in[i];      \
         (wk).base[i] = bi;              \
         bad |= (unsigned)bi >= lim;     \
     }
-#define WG_STATE_TEST(GOOD, in, PH_OK, n0, m0, rows, ROW, MORE)                                      \
-    const int ph = (in).phase[k];                                                                    \
-    const long long q1 = (in).pivots[2 * (size_t)k], q2 = (in).pivots[2 * (size_t)k + 1];            \
+#define WG_GROWN_ROW(wk, m0)                                                                         \
+    {                                                                                                \
+        const int bi = i < (m0) ? base_in[i] : n + i; /* a new row's slack is basic */               \
+        (wk).base[i] = bi;                                                                           \
+        bad |= i < (m0) && (unsigned)bi >= lim;                                                      \
+    }
+#define WG_STATE_TEST(GOOD, in, sk, PH_OK, n0, m0, rows, ROW, MORE)                                  \
+    const int ph = (in).phase[sk];                                                                   \
+    const long long q1 = (in).pivots[2 * (size_t)(sk)], q2 = (in).pivots[2 * (size_t)(sk) + 1];      \
     GOOD = (PH_OK) && q1 >= 0 && q2 >= 0;                                                            \
+    WG_STATE_BASIS(in, sk, n0, m0, rows, ROW, MORE)
+// ... and its second half alone, the basis, for the kernel that has ph and `good` by then
+// (k_batch_solve_branch, which must range-test sk before it reads the phase and the counts).
+#define WG_STATE_BASIS(in, sk, n0, m0, rows, ROW, MORE)                                              \
     if (good) {                                                                                      \
         const unsigned lim = ph == 1 ? (unsigned)((n0) + 2 * (m0)) : (unsigned)((n0) + (m0));        \
-        const int *base_in = (in).base + (size_t)k * (size_t)(m0);                                   \
+        const int *base_in = (in).base + (size_t)(sk) * (size_t)(m0);                                \
         int bad = 0;                                                                                 \
         for (int i = threadIdx.x; i < (rows); i += SX_TILE) ROW                                      \
         MORE                                                                                         \
         good = !__syncthreads_or(bad);                                                               \
     }
+
+// WG_LOAD_GROWN -- the in-state of problem sk, shape (n, m0 = m - q), into the working set of the shape
+// grown by q rows, for the kernels that declare m0, Ns0, N10 and cells0 beside the head's names: the
+// dense in-state is walked at its stride Ns0 into the grown shape's odd ld (wg_load_T), old rows end in
+// q entries of +0.0 (the new slack columns), d ends in +0.0 from Ns0 on.  The basis, with the new rows'
+// basic slacks, is WG_STATE_TEST's with WG_GROWN_ROW.  Ends behind a barrier.
+#define WG_LOAD_GROWN(in, sk, q)                                                                     \
+    do {                                                                                             \
+        wg_load_T(w, (in).T + (size_t)(sk) * (size_t)cells0, Ns0, cells0);                           \
+        for (int x = threadIdx.x; x < m0 * (q); x += SX_TILE) {                                      \
+            const int i = x / (q);                                                                   \
+            w.T[(size_t)i * w.ld + Ns0 + (x - i * (q))] = 0.0;                                       \
+        }                                                                                            \
+        const double *d_in = (in).d + (size_t)(sk) * (size_t)N10;                                    \
+        for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;            \
+        __syncthreads();                                                                             \
+    } while (0)
+
+// WG_REDUCE_ROW -- new row r of a grown working set reduced against the kept basis, a row operation
+// on the grown system.  Declares row = T[r]; the multipliers f_i = MULT (an
+// expression with i and bi = base[i] in scope: the raw row's entry in the column of old row i's basic
+// variable, +0.0 for a basic slack) are staged once in colE (m >= m0 doubles, free by then); behind a
+// barrier consecutive lanes take consecutive columns j -- the reads of T[i][j] are row-contiguous --
+// and row[j] = RAW (an expression with j and row in scope: the raw row's entry), then
+// fma(-f_i, T[i][j], .) for i = 0 .. m0 - 1 in that order.  Ends behind a barrier: colE may be
+// rewritten for the next row, and T is complete behind the last.
+#define WG_REDUCE_ROW(r, MULT, RAW)                                                                  \
+    do {                                                                                             \
+        double *row = w.T + (size_t)(r) * w.ld;                                                      \
+        for (int i = threadIdx.x; i < m0; i += SX_TILE) {                                            \
+            const int bi = w.base[i];                                                                \
+            w.colE[i] = MULT;                                                                        \
+        }                                                                                            \
+        __syncthreads();                                                                             \
+        for (int j = threadIdx.x; j < Ns; j += SX_TILE) {                                            \
+            double acc = RAW;                                                                        \
+            for (int i = 0; i < m0; ++i) acc = fma(-w.colE[i], w.T[(size_t)i * w.ld + j], acc);      \
+            row[j] = acc;                                                                            \
+        }                                                                                            \
+        __syncthreads();                                                                             \
+    } while (0)
 
 // WG_DUAL_LOST -- is the row d of the carve wk, N wide, no longer dual feasible?  wg_solve's entering
 // selection and stop test, into `lost`.
@@ -563,10 +618,11 @@ __device__ __forceinline__ void wg_load_T(const BatchWork &wk, const double *T_i
     }
 
 // WG_COLD_START -- the problem is built from A, b, c and solved as k_batch_solve_dev does, at the
-// sites every path shares: phase 1's tableau and canonical row, no pivot behind it.
-#define WG_COLD_START(t, dual)           \
+// sites every path shares: phase 1's tableau and canonical row, no pivot behind it.  BUILD is the
+// kernel's build of the working set, wg_build(...) or, of a composite problem, wg_build_branch(...).
+#define WG_COLD_START(t, dual, BUILD)    \
     do {                                 \
-        wg_build(w, src, by_col);        \
+        BUILD;                           \
         wg_update_objective(w, N1);      \
         (t).p1 = (t).p2 = 0;             \
         (t).ph2 = dual = false;          \
@@ -774,7 +830,7 @@ __global__ __launch_bounds__(SX_TILE) void k_batch_solve_st(BatchStArgs a) {
             wg_build(w, src, by_col);
             wg_update_objective(w, N1);
         } else {
-            WG_STATE_TEST(good, a.in, ph == 1 || ph == 2, n, m, m, WG_BASE_ROW(w), );
+            WG_STATE_TEST(good, a.in, k, ph == 1 || ph == 2, n, m, m, WG_BASE_ROW(w), );
             if (good) {
                 // consecutive lanes walk the dense rows; the working set's stride is the odd ld
                 WG_LOAD_STATE(a.in);
@@ -835,7 +891,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) 
                            rerhs ? a.b + (long long)k * a.b_sb : nullptr, a.b_si, a.c + (long long)k * a.c_sb, a.c_sj};
         TwoPhase t{SX_BAD_STATE, false, 0, 0};
         bool dual = false;  // the problem stands inside the dual loop
-        WG_STATE_TEST(bool good, a.in, ph >= 1 && ph <= 3, n, m, m, WG_BASE_ROW(w), );
+        WG_STATE_TEST(bool good, a.in, k, ph >= 1 && ph <= 3, n, m, m, WG_BASE_ROW(w), );
         if (good) {
             bool cold = rerhs && ph == 1;
             if (!cold) {
@@ -852,7 +908,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) 
                 if (rerhs) WG_DUAL_LOST(cold, w, Ns);
             }
             if (cold) {
-                WG_COLD_START(t, dual);
+                WG_COLD_START(t, dual, wg_build(w, src, by_col));
             } else if (rerhs) {
                 // T[i][0] = S[i][.] b' and, as row m, d[0] = y b'
                 for (int i = threadIdx.x; i <= m; i += SX_TILE) {
@@ -875,16 +931,14 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rhs(BatchRhsArgs a) 
 // system is [D' b' | D' A' | D'] with D' = diag(D, I), and a new row minus a combination of old rows is
 // a row operation on it, so the grown tableau is again M' [D' b' | D' A' | D'] with the slack block
 // S' = [[S, 0], [-f^T S, I]]: k_batch_solve_rhs's identities hold on it.
-// Load: the dense in-state is walked at its stride 1 + n + m0 into the grown working set (odd ld of
-// the grown shape), old rows end in q entries of +0.0, d ends in +0.0 from 1 + n + m0 on, and the new
-// rows' slacks are basic.  A phase-1 state, or a row d that is not dual feasible, is a cold start from
-// A, b, c (WG_COLD_START).  Warm start, per new row t: the multipliers f_i = the row's
-// entry in the column of old row i's basic variable (+0.0 for a basic slack) are staged in colE, then
-// consecutive lanes take consecutive columns j -- the reads of T[i][j] are row-contiguous -- and
-// T[m0 + t][j] = the raw row's entry, then fma(-f_i, T[i][j], .) for i = 0 .. m0 - 1 in that order.
-// The new rows do not depend on each other, d is unchanged, pivots[0] is kept and pivots[1] = 0; then
-// the dual loop from 0 and phase 2 at the same count (WG_KEPT_TAIL).  Only rows m0 .. m of A and b are
-// read unless the problem is cold.  The state's tests are k_batch_solve_rhs's against the in-state's shape.
+// The front is the row-growing one, which k_batch_solve_branch and k_batch_solve_cut share: the
+// state's tests against the in-state's shape with the new rows' slacks basic (WG_STATE_TEST with
+// WG_GROWN_ROW), the load (WG_LOAD_GROWN), and per new row the reduction against the kept basis
+// (WG_REDUCE_ROW).  A phase-1 state, or a row d that is not dual feasible, is a cold start from A, b, c
+// (WG_COLD_START).  This kernel's own: a new row is read, row r of A and b through their strides, with
+// its unit slack.  The new rows do not depend on each other, d is unchanged, pivots[0] is kept and
+// pivots[1] = 0; then the dual loop from 0 and phase 2 at the same count (WG_KEPT_TAIL).  Only rows
+// m0 .. m of A and b are read unless the problem is cold.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a) {
     WG_KEPT_HEAD(a, sc);
@@ -898,48 +952,22 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_rows(BatchRowsArgs a
                            a.c + (long long)k * a.c_sb, a.c_sj};
         TwoPhase t{SX_BAD_STATE, false, 0, 0};
         bool dual = false;  // the problem stands inside the dual loop
-        // the in-state's own range: what is valid only for the grown shape is refused
-        WG_STATE_TEST(
-            bool good, a.in, ph >= 1 && ph <= 3, n, m0, m,
-            {
-                const int bi = i < m0 ? base_in[i] : n + i;  // a new row's slack is basic
-                w.base[i] = bi;
-                bad |= i < m0 && (unsigned)bi >= lim;
-            }, );
+        WG_STATE_TEST(bool good, a.in, k, ph >= 1 && ph <= 3, n, m0, m, WG_GROWN_ROW(w, m0), );
         if (good) {
             bool cold = ph == 1;
             if (!cold) {
-                // the in-state's rows at the grown shape's odd ld
-                wg_load_T(w, a.in.T + (size_t)k * (size_t)cells0, Ns0, cells0);
-                for (int x = threadIdx.x; x < m0 * q; x += SX_TILE) {
-                    const int i = x / q;
-                    w.T[(size_t)i * w.ld + Ns0 + (x - i * q)] = 0.0;
-                }
-                const double *d_in = a.in.d + (size_t)k * (size_t)N10;
-                for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;
-                __syncthreads();
+                WG_LOAD_GROWN(a.in, k, q);
                 WG_DUAL_LOST(cold, w, Ns);  // at the grown width
             }
             if (cold) {
-                WG_COLD_START(t, dual);
+                WG_COLD_START(t, dual, wg_build(w, src, by_col));
             } else {
                 for (int r = m0; r < m; ++r) {
                     const double *Ar = src.A + (long long)r * src.A_sr;
-                    // the multipliers of the row, once, in colE (m >= m0 doubles, free by now)
-                    for (int i = threadIdx.x; i < m0; i += SX_TILE) {
-                        const int bi = w.base[i];
-                        w.colE[i] = bi < n ? Ar[(long long)bi * src.A_sc] : 0.0;
-                    }
-                    __syncthreads();
-                    double *row = w.T + (size_t)r * w.ld;
-                    for (int j = threadIdx.x; j < Ns; j += SX_TILE) {
-                        double acc = j == 0   ? src.b[(long long)r * src.b_si]
-                                     : j <= n ? Ar[(long long)(j - 1) * src.A_sc]
-                                              : (j - 1 - n == r ? 1.0 : 0.0);
-                        for (int i = 0; i < m0; ++i) acc = fma(-w.colE[i], w.T[(size_t)i * w.ld + j], acc);
-                        row[j] = acc;
-                    }
-                    __syncthreads();  // colE is rewritten for the next row; T is complete behind the last
+                    WG_REDUCE_ROW(r, bi < n ? Ar[(long long)bi * src.A_sc] : 0.0,
+                                  j == 0   ? src.b[(long long)r * src.b_si]
+                                  : j <= n ? Ar[(long long)(j - 1) * src.A_sc]
+                                           : (j - 1 - n == r ? 1.0 : 0.0));
                 }
                 t.p1 = q1;
                 t.p2 = 0;
@@ -985,7 +1013,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a
         bool dual = false;  // the problem stands inside the dual loop
         // the in-state's own range: what is valid only for the grown shape is refused
         WG_STATE_TEST(
-            bool good, a.in, ph >= 1 && ph <= 3, n0, m, m,
+            bool good, a.in, k, ph >= 1 && ph <= 3, n0, m, m,
             {
                 const int bi = base_in[i];
                 w.base[i] = bi >= n0 ? bi + p : bi;  // a slack moves up with its column
@@ -1022,7 +1050,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cols(BatchColsArgs a
                 if (ph == 3) WG_DUAL_LOST(cold, w, Ns);  // at the grown width
             }
             if (cold) {
-                WG_COLD_START(t, dual);
+                WG_COLD_START(t, dual, wg_build(w, src, by_col));
             } else {
                 t.p1 = q1;
                 t.p2 = 0;
@@ -1199,7 +1227,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a
         const int *ix = a.idx + (size_t)k * (size_t)q;
         // the in-state's own range, and the list: strictly ascending inside that shape
         WG_STATE_TEST(
-            bool good, a.in, ph >= 1 && ph <= 3, n0, m0, m0, WG_BASE_ROW(w0),
+            bool good, a.in, k, ph >= 1 && ph <= 3, n0, m0, m0, WG_BASE_ROW(w0),
             for (int j = threadIdx.x; j < q; j += SX_TILE) {
                 const int v = ix[j];
                 bad |= (unsigned)v >= (unsigned)(kind == 0 ? m0 : n0) || (j > 0 && ix[j - 1] >= v);
@@ -1228,7 +1256,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_drop(BatchDropArgs a
                 }
             }
             if (cold) {
-                WG_COLD_START(t, dual);
+                WG_COLD_START(t, dual, wg_build(w, src, by_col));
             } else {
                 t.p1 = q1;
                 t.p2 = forced;
@@ -1279,14 +1307,14 @@ __device__ __forceinline__ void wg_build_branch(const BatchWork &w, const SxSour
 // rows (q = a.depth); behind the root's rows come the child's q bound rows cf[t] x_var[t] <= rh[t], of
 // which the first q - 1 are what the parent was solved with and the last one is new.  No dense row
 // exists: the new row's raw entries are rh[q - 1] | cf[q - 1] at column var[q - 1], +0.0 elsewhere | the
-// unit slack, its multipliers are cf[q - 1] where base[i] == var[q - 1] and +0.0 elsewhere, and the
-// chain over the old rows is k_batch_solve_rows's, whole, so every bit is that kernel's on the explicit
-// grown problem.  The cold start builds the composite problem (wg_build_branch).
-// The front is this kernel's own because it indexes the in-state with pk and the source with rk, where
-// WG_STATE_TEST and WG_LOAD_STATE know the one name k; results and out-state are written at k, so the
-// tail and the end are the shared ones.  pk, rk and the q variables are tested before anything is
-// indexed with them, then the in-state as k_batch_solve_rows tests it; a child that fails gets
-// SX_BAD_STATE and cleared outputs.
+// unit slack, and its multipliers are cf[q - 1] where base[i] == var[q - 1] and +0.0 elsewhere; these
+// go to the shared chain (WG_REDUCE_ROW), so every bit is k_batch_solve_rows's on the explicit grown
+// problem.  The cold start builds the composite problem (wg_build_branch).
+// The in-state is indexed with pk and the source with rk; results and out-state are written at k.  pk,
+// rk and the q variables are tested before anything is indexed with them, so the phase and the pivot
+// counts are read here, under that test, and not by WG_STATE_TEST, which reads them unconditionally;
+// the basis test is its second half (WG_STATE_BASIS).  A child that fails gets SX_BAD_STATE and
+// cleared outputs.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_branch(BatchBranchArgs a) {
     WG_KEPT_HEAD(a, sc);
@@ -1305,7 +1333,7 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_branch(BatchBranchAr
         int off = 0;
         for (int j = threadIdx.x; j < q; j += SX_TILE) off |= (unsigned)var[j] >= (unsigned)n;
         bool good = !__syncthreads_or(off) && (unsigned)pk < (unsigned)a.parents && (unsigned)rk < (unsigned)a.roots;
-        // the in-state's own tests, against its shape: k_batch_solve_rows's, at pk
+        // the in-state's own tests, against its shape, at pk: only a pk in range is read
         int ph = 0;
         long long q1 = 0, q2 = 0;
         if (good) {
@@ -1314,48 +1342,22 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_branch(BatchBranchAr
             q2 = a.in.pivots[2 * (size_t)pk + 1];
             good = ph >= 1 && ph <= 3 && q1 >= 0 && q2 >= 0;
         }
-        if (good) {
-            const unsigned lim = ph == 1 ? (unsigned)(n + 2 * m0) : (unsigned)(n + m0);
-            const int *base_in = a.in.base + (size_t)pk * (size_t)m0;
-            int bad = 0;
-            for (int i = threadIdx.x; i < m; i += SX_TILE) {
-                const int bi = i < m0 ? base_in[i] : n + i;  // the new row's slack is basic
-                w.base[i] = bi;
-                bad |= i < m0 && (unsigned)bi >= lim;
-            }
-            good = !__syncthreads_or(bad);
-        }
+        WG_STATE_BASIS(a.in, pk, n, m0, m, WG_GROWN_ROW(w, m0), );
         if (good) {
             const SxSource src{a.A + (long long)rk * a.A_sb, a.A_sr, a.A_sc, a.b + (long long)rk * a.b_sb, a.b_si,
                                a.c + (long long)rk * a.c_sb, a.c_sj};
             bool cold = ph == 1;
             if (!cold) {
-                // the parent's rows at the child's odd ld, each ending in +0.0 for the new slack
-                wg_load_T(w, a.in.T + (size_t)pk * (size_t)cells0, Ns0, cells0);
-                for (int i = threadIdx.x; i < m0; i += SX_TILE) w.T[(size_t)i * w.ld + Ns0] = 0.0;
-                const double *d_in = a.in.d + (size_t)pk * (size_t)N10;
-                for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;
-                __syncthreads();
+                WG_LOAD_GROWN(a.in, pk, 1);
                 WG_DUAL_LOST(cold, w, Ns);  // at the child's width
             }
             if (cold) {
-                wg_build_branch(w, src, by_col, mA, var, cf, rh);
-                wg_update_objective(w, N1);
-                t.p1 = t.p2 = 0;
-                t.ph2 = dual = false;
+                WG_COLD_START(t, dual, wg_build_branch(w, src, by_col, mA, var, cf, rh));
             } else {
                 const int v = var[q - 1];
                 const double cv = cf[q - 1], rv = rh[q - 1];
-                // the multipliers of the new row, once, in colE (m >= m0 doubles, free by now)
-                for (int i = threadIdx.x; i < m0; i += SX_TILE) w.colE[i] = w.base[i] == v ? cv : 0.0;
-                __syncthreads();
-                double *row = w.T + (size_t)m0 * w.ld;
-                for (int j = threadIdx.x; j < Ns; j += SX_TILE) {
-                    double acc = j == 0 ? rv : j <= n ? (j - 1 == v ? cv : 0.0) : (j - 1 - n == m0 ? 1.0 : 0.0);
-                    for (int i = 0; i < m0; ++i) acc = fma(-w.colE[i], w.T[(size_t)i * w.ld + j], acc);
-                    row[j] = acc;
-                }
-                __syncthreads();  // T is complete
+                WG_REDUCE_ROW(m0, bi == v ? cv : 0.0,
+                              j == 0 ? rv : j <= n ? (j - 1 == v ? cv : 0.0) : (j - 1 - n == m0 ? 1.0 : 0.0));
                 t.p1 = q1;
                 t.p2 = 0;
                 t.ph2 = dual = true;
@@ -1387,8 +1389,9 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_branch(BatchBranchAr
 // call's, not the compiler's, so the q accumulators of a single pass have no registers to live in.
 // Every other cut is the null row, +0.0 throughout; a cold problem's cuts are all null, so its
 // composite build is wg_build_branch's with +0.0 coefficients and right-hand sides (staged in colE).
-// Then k_batch_solve_rows's chain per new row, the multipliers staged in colE from the raw row before
-// the chain overwrites it, the shared tail and the shared end.
+// The state's tests, the load and the reduction of each new row are the row-growing front's
+// (k_batch_solve_rows), the multipliers taken from the raw row where it stands before the chain
+// overwrites it; then the shared tail and the shared end.
 template <bool LDS>
 __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cut(BatchCutArgs a) {
     WG_KEPT_HEAD(a, sc);
@@ -1406,25 +1409,10 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cut(BatchCutArgs a) 
         int *const crow = a.cut_row + (size_t)k * (size_t)q;
         TwoPhase t{SX_BAD_STATE, false, 0, 0};
         bool dual = false;  // the problem stands inside the dual loop
-        // the in-state's own range: what is valid only for the grown shape is refused
-        WG_STATE_TEST(
-            bool good, a.in, ph >= 1 && ph <= 3, n, m0, m,
-            {
-                const int bi = i < m0 ? base_in[i] : n + i;  // a new row's slack is basic
-                w.base[i] = bi;
-                bad |= i < m0 && (unsigned)bi >= lim;
-            }, );
+        WG_STATE_TEST(bool good, a.in, k, ph >= 1 && ph <= 3, n, m0, m, WG_GROWN_ROW(w, m0), );
         bool cold = !good || ph == 1;
         if (!cold) {
-            // the in-state's rows at the grown shape's odd ld
-            wg_load_T(w, a.in.T + (size_t)k * (size_t)cells0, Ns0, cells0);
-            for (int x = threadIdx.x; x < m0 * q; x += SX_TILE) {
-                const int i = x / q;
-                w.T[(size_t)i * w.ld + Ns0 + (x - i * q)] = 0.0;
-            }
-            const double *d_in = a.in.d + (size_t)k * (size_t)N10;
-            for (int j = threadIdx.x; j < N1; j += SX_TILE) w.d[j] = j < Ns0 ? d_in[j] : 0.0;
-            __syncthreads();
+            WG_LOAD_GROWN(a.in, k, q);
             WG_DUAL_LOST(cold, w, Ns);  // at the grown width
         }
         if (cold) {
@@ -1443,10 +1431,9 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cut(BatchCutArgs a) 
                 // the composite build of the m0 rows read and q rows of +0.0
                 for (int tt = threadIdx.x; tt < q; tt += SX_TILE) w.colE[tt] = 0.0;
                 __syncthreads();
-                wg_build_branch(w, src, by_col, m0, reinterpret_cast<const int *>(w.colE), w.colE, w.colE);
-                wg_update_objective(w, N1);
-                t.p1 = t.p2 = 0;
-                t.ph2 = dual = false;
+                WG_COLD_START(
+                    t, dual,
+                    wg_build_branch(w, src, by_col, m0, reinterpret_cast<const int *>(w.colE), w.colE, w.colE));
             } else {
                 const bool usable = ph == 2;
                 for (int i = threadIdx.x; i < m0; i += SX_TILE) w.colE[i] = 0.0;  // no row is taken yet
@@ -1523,22 +1510,8 @@ __global__ __launch_bounds__(SX_TILE, 4) void k_batch_solve_cut(BatchCutArgs a) 
                     }
                     __syncthreads();
                 }
-                // k_batch_solve_rows's chain, the raw row read from where it stands
-                for (int r = m0; r < m; ++r) {
-                    double *row = w.T + (size_t)r * w.ld;
-                    // the multipliers of the row, once, in colE, before the chain overwrites the row
-                    for (int i = threadIdx.x; i < m0; i += SX_TILE) {
-                        const int bi = w.base[i];
-                        w.colE[i] = bi < n ? row[1 + bi] : 0.0;
-                    }
-                    __syncthreads();
-                    for (int j = threadIdx.x; j < Ns; j += SX_TILE) {
-                        double acc = row[j];
-                        for (int i = 0; i < m0; ++i) acc = fma(-w.colE[i], w.T[(size_t)i * w.ld + j], acc);
-                        row[j] = acc;
-                    }
-                    __syncthreads();  // colE is rewritten for the next row; T is complete behind the last
-                }
+                // the raw row read from where it stands: the multipliers before the chain overwrites it
+                for (int r = m0; r < m; ++r) WG_REDUCE_ROW(r, bi < n ? row[1 + bi] : 0.0, row[j]);
                 t.p1 = q1;
                 t.p2 = 0;
                 t.ph2 = dual = true;

@@ -4,8 +4,9 @@ optional outputs left NULL, a caller-made workspace.  ctypes over _lib.BatchDevi
 
   workspace                    simplex_batch_device_workspace
   batch_device                 simplex_solve_batch_device, simplex_solve_batch_device_ragged
-  kept_call                    simplex_solve_batch_device_state, _rhs, _rows, _cols, _drop
-                               (state_call, rhs_call, rows_call, cols_call, drop_call)
+  kept_call                    simplex_solve_batch_device_state, _rhs, _rows, _cols, _drop, _branch, _cut
+                               (state_call, rhs_call, rows_call, cols_call, drop_call, branch_call, cut_call;
+                               branch_struct and cut_struct build the last two's own argument)
   solve_device                 simplex_solve_device
   build_phase1_device          simplex_dev_build_phase1_device
 
@@ -205,6 +206,55 @@ def drop_call(n, m, count, A, b, c, state_in, kind, idx, state_out=None, ws_shap
     sized for the in-state's shape unless ws_shape says otherwise"""
     return kept_call("simplex_solve_batch_device_drop", n, m, count, A, b, c, state_in, state_out, kind, idx.shape[1],
                      idx.data_ptr(), ws_shape=ws_shape or (state_in.n, state_in.m), **kw)
+
+
+def _addr(t):
+    """a tensor's address; a raw address or None as it is"""
+    return t.data_ptr() if isinstance(t, torch.Tensor) else t
+
+
+def branch_struct(roots, parents, depth, root, parent, var, coef, rhs):
+    """a simplex_batch_branch_t over dense device tensors (or raw addresses / None)"""
+    return _lib.BatchBranchT(roots=roots, parents=parents, depth=depth, root=_addr(root), parent=_addr(parent),
+                             var=_addr(var), coef=_addr(coef), rhs=_addr(rhs))
+
+
+def branch_call(n, m, count, A, b, c, state_in, roots, parent, var, coef, rhs, root=None, state_out=None, **kw):
+    """on the children's shape (n, m) and number; A, b, c are Srcs of `roots` problems of m - q rows with
+    explicit strides (a batch stride of 0 for one root), state_in has the shape (n, m - 1); parent, root
+    (None: parent), var, coef and rhs are dense device tensors"""
+    for t, dtype in ((parent, torch.int32), (var, torch.int32), (coef, torch.float64), (rhs, torch.float64)):
+        assert t.dtype == dtype and t.is_contiguous() and t.shape[0] == count
+    root = parent if root is None else root
+    assert root.dtype == torch.int32 and root.is_contiguous() and tuple(root.shape) == (count,)
+    br = branch_struct(roots, state_in.phase.shape[0], var.shape[1], root, parent, var, coef, rhs)
+    return kept_call("simplex_solve_batch_device_branch", n, m, count, A, b, c, state_in, state_out, ctypes.byref(br),
+                     **kw)
+
+
+def cut_struct(cuts=1, away=0.05, integer=None, integer_sb=0, integer_sj=1, row=None, cut_A=None, cut_A_sb=0, cut_A_sr=0,
+               cut_A_sc=0, cut_b=None, cut_b_sb=0, cut_b_si=0, cut_row=None):
+    """a simplex_batch_cut_t over device tensors (or raw addresses / None)"""
+    return _lib.BatchCutT(cuts=cuts, away=away, integer=_addr(integer), integer_sb=integer_sb, integer_sj=integer_sj,
+                          row=_addr(row), cut_A=_addr(cut_A), cut_A_sb=cut_A_sb, cut_A_sr=cut_A_sr, cut_A_sc=cut_A_sc,
+                          cut_b=_addr(cut_b), cut_b_sb=cut_b_sb, cut_b_si=cut_b_si, cut_row=_addr(cut_row))
+
+
+def cut_call(n, m, count, A, b, c, state_in, integer, cuts=1, away=0.05, row=None, state_out=None, **kw):
+    """on the grown shape (n, m); A and b are Srcs of the m - cuts rows state_in (shape (n, m - cuts)) was
+    solved with, integer a uint8 [count, n] or [n] device tensor with its own strides, row None or a dense
+    int32 [count, cuts] one.  The cuts go to dense buffers of their own instead of the rows behind the
+    source's, pre-filled with SENTINEL: o.cut_A [count, cuts, n], o.cut_b [count, cuts], o.cut_row
+    [count, cuts]"""
+    assert integer.dtype == torch.uint8 and integer.shape[-1] == n
+    cut_A = torch.full((count, cuts, n), SENTINEL, dtype=torch.float64, device="cuda")
+    cut_b = torch.full((count, cuts), SENTINEL, dtype=torch.float64, device="cuda")
+    cut_row = torch.full((count, cuts), int(SENTINEL), dtype=torch.int32, device="cuda")
+    cut = cut_struct(cuts, away, integer, integer.stride(0) if integer.dim() == 2 else 0, integer.stride(-1), row,
+                     cut_A, *cut_A.stride(), cut_b, *cut_b.stride(), cut_row)
+    o = kept_call("simplex_solve_batch_device_cut", n, m, count, A, b, c, state_in, state_out, ctypes.byref(cut), **kw)
+    o.cut_A, o.cut_b, o.cut_row = cut_A, cut_b, cut_row
+    return o
 
 
 def as_batch_tensors(o, n_k=None, m_k=None, keep=None):

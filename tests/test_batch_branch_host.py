@@ -16,7 +16,7 @@ from batch_branch_refs import (PARENTS, THETAS, branch_shapes, explicit, is_cold
                                want_two_children, LEVEL1, LEVEL2)
 from batch_rows_refs import ref_rows, rows_instances
 from batch_state_refs import bits, ref_state, same_fields
-from branch_entries import branch_struct
+from device_entries import branch_struct
 from simplexoncuda_amd import _lib
 from test_batch_rows_host import ROUNDING  # the bound that file accepts for the rows entry, reused
 

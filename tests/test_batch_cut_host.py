@@ -22,7 +22,7 @@ import simplexoncuda_amd as sx
 from batch_cut_refs import (AWAY, SCALES, frac, grown_arrays, masks, mixed_cut_instances, ref_cut, usable, want_cut)
 from batch_rows_refs import rows_shapes
 from batch_state_refs import ref_state
-from cut_entries import cut_struct
+from device_entries import cut_struct
 from simplexoncuda_amd import _lib
 
 # Measured by the tests below (they print the figures); each bound leaves a margin of 100 over its figure.

@@ -1,5 +1,5 @@
 """Branching a kept batch state (simplex_solve_batch_device_branch, sx_batch.hip k_batch_solve_branch)
-through sx.branch_batch_tensors, and through a ctypes caller (branch_entries.branch_call) for what that
+through sx.branch_batch_tensors, and through a ctypes caller (device_entries.branch_call) for what that
 never passes.  Needs an MI355X.
 
 Everything is compared bit for bit, without a tolerance, against batch_branch_refs.py: the existing
@@ -20,8 +20,7 @@ from batch_branch_refs import (EDGE_SHAPES, LEVEL1, LEVEL2, PARENTS, THETAS, bou
 from batch_refs import same_tensors, tensors
 from batch_rows_refs import CAP_SHAPE, ROWS_CAPS, optimum, rows_instances
 from batch_state_refs import bits, ref_state, same_as_state_refs, state_tensors
-from branch_entries import branch_call
-from device_entries import Src, dense, flipped, unchanged
+from device_entries import Src, branch_call, dense, flipped, unchanged
 
 pytestmark = pytest.mark.gpu
 

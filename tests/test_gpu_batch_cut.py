@@ -1,5 +1,5 @@
 """Gomory mixed-integer cuts from a kept batch state (simplex_solve_batch_device_cut, sx_batch.hip
-k_batch_solve_cut) through sx.cut_batch_tensors, and through a ctypes caller (cut_entries.cut_call) for what
+k_batch_solve_cut) through sx.cut_batch_tensors, and through a ctypes caller (device_entries.cut_call) for what
 that never passes.  Needs an MI355X.
 
 Everything is compared bit for bit, without a tolerance, against batch_cut_refs.py: the entry restated from
@@ -17,8 +17,7 @@ from batch_refs import same_as_refs, same_tensors, tensors
 from batch_rhs_refs import DBL_MAX, ref_rhs, ref_rhs_resume, scaled_rhs
 from batch_rows_refs import lds_edge, rows_shapes
 from batch_state_refs import bits, many_instances, ref_state, same_as_state_refs, state_tensors
-from cut_entries import cut_call
-from device_entries import SENTINEL, dense
+from device_entries import SENTINEL, cut_call, dense
 
 pytestmark = pytest.mark.gpu
 
