@@ -1275,6 +1275,70 @@ constexpr int kOS = 7;
 constexpr int kOM = 8;
 constexpr int kOU = 9;  // (odd: a history value's low word at kOU + 2s, its high word after it)
 
+// ---- The steps of a pivot that the one-shard fused batch (k_batch) and the multi-rank one
+// (batch_mr_body) share, each written once (every one leaves the instructions of
+// all three kernels as they were; what else the two bodies have in common moved some and stays
+// written out).  t is the caller's threadIdx.x: reading it again here moves k_batch's instructions.
+
+// Pass 1 of an objective tile's argmin (reduction.cu:51-80), first step: every half-wave its tree
+// and its winner into s_v / s_i.  The caller's block barrier follows.
+__device__ __forceinline__ void tile_halves(int t, double v, int i, double (&s_v)[16], int (&s_i)[16]) {
+    half_argmin(v, i);
+    if ((t & 31) == 0) {
+        s_v[t >> 5] = v;
+        s_i[t >> 5] = i;
+    }
+}
+// A tile winner (v, i), as wave 0's second half_argmin leaves it in lane 0, made wave-uniform.
+__device__ __forceinline__ void wave_uniform(double &v, int &i) {
+    i = __builtin_amdgcn_readfirstlane(i);
+    const long long vb = __double_as_longlong(v);
+    v = __longlong_as_double(((long long)__builtin_amdgcn_readfirstlane((int)(vb >> 32)) << 32) |
+                             (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)vb));
+}
+
+// The leaving row's details out of its tile's ratio record (granules kRD.. gathered into s_g) into
+// LDS, by wave 0: F[r][s] of this stage's slots, and by thread 0 d_e, p, the RHS, e and the ratio
+// side's status.
+__device__ __forceinline__ void details_in(int t, int q, int qq, int r, const unsigned *s_g, double *s_fr, double *s_p,
+                                           int *s_r, int *s_e, double &det_dmin, double &br, int &det_e, int &det_st) {
+    if (t < qq) s_fr[t] = gd(s_g[kRF - kRD + 2 * t], s_g[kRF - kRD + 1 + 2 * t]);
+    if (t == 0) {
+        det_dmin = gd(s_g[0], s_g[1]);
+        s_p[q] = gd(s_g[kRA - kRD], s_g[kRA - kRD + 1]);
+        br = gd(s_g[kRB - kRD], s_g[kRB - kRD + 1]);
+        det_e = (int)s_g[kRE - kRD];
+        det_st = (int)s_g[kRS - kRD];
+        s_r[q] = r;
+        s_e[q] = (int)s_g[kRE - kRD];
+    }
+}
+
+// The objective tile's own update by a pivot (updateCostsVector, solver.cu:48-56): d of this
+// thread's column from its current pivot-row value u (first: thread 0 of tile 0, d[0] from the
+// pivot row's RHS), and the column as the tile's candidate (v, i).
+__device__ __forceinline__ void obj_update(double dmin, double p, double br, double u, bool first, bool liveB, int ia,
+                                           double &d0, double &dj, double &v, int &i) {
+    const double fd = -dmin / p;
+    if (first) d0 = fma(fd, br, d0);
+    if (liveB) {
+        dj = fma(fd, u, dj);
+        if (cmp_eps(dj, v) < 0) {
+            v = dj;
+            i = ia;
+        }
+    }
+}
+
+// Pivot q into the batch's records, for the sweep (thread 0 of a shard's ratio tile 0; base[r] = e,
+// solver.cu:105, follows at the end of the batch).
+__device__ __forceinline__ void record_pivot(PivRec *recs, double *U, size_t ld, int q, int r, int e, double p, double br) {
+    recs[q].r = r;
+    recs[q].e = e;
+    recs[q].p = p;
+    U[(size_t)q * ld] = br;  // the pivot row's RHS entry
+}
+
 // K6: a whole batch of pivots in ONE resident launch (one shard).  Blocks [0, NA) own the
 // 512-row ratio tiles, blocks [NA, NA + NB) the 512-entry objective-row tiles.  Each block
 // keeps its slice of the state on chip for the whole batch: a ratio block its rows' current
@@ -1448,17 +1512,13 @@ __global__ __launch_bounds__(512) void k_batch(const double *T, int rows, size_t
                 if ((t & 63) == 0) s_welig[t >> 6] = anyw;
                 __syncthreads();
                 if (t < 64) {
-                    double v = t < 16 ? s_v[t] : DBL_MAX;
-                    int i = t < 16 ? s_i[t] : -1;
-                    half_argmin(v, i);
+                    double wv = t < 16 ? s_v[t] : DBL_MAX;
+                    int wi = t < 16 ? s_i[t] : -1;
+                    half_argmin(wv, wi);
                     int any = 0;
 #pragma unroll
                     for (int w = 0; w < SX_TILE / 64; ++w) any |= s_welig[w];
-                    const int wi = __builtin_amdgcn_readfirstlane(i);
-                    const long long vb = __double_as_longlong(v);
-                    const double wv = __longlong_as_double(
-                        ((long long)__builtin_amdgcn_readfirstlane((int)(vb >> 32)) << 32) |
-                        (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)vb));
+                    wave_uniform(wv, wi);
                     const int wl = wi >= 0 ? wi - (int)blockIdx.x * SX_TILE : 0;
                     const unsigned pl = (wi >= 0 ? (unsigned)wl : SX_NOIDX) | ((unsigned)any << 10);
                     const int nG = kRF + 2 * qq;
@@ -1544,10 +1604,7 @@ __global__ __launch_bounds__(512) void k_batch(const double *T, int rows, size_t
                     }
                 }
                 if (blockIdx.x == 0 && t == 0) {  // (base[r] = e, solver.cu:105: at the end of the batch)
-                    recs[q].r = r;
-                    recs[q].e = e;
-                    recs[q].p = p;
-                    U[(size_t)q * ld] = br;  // the pivot row's RHS entry, for the sweep
+                    record_pivot(recs, U, ld, q, r, e, p, br);
                 }
                 // ---- the objective side's answer: pass 2 over the objective tiles (the entering variable
                 // of pivot q + 1), its stored column and its pivot-row entry of this pivot from the
@@ -1645,16 +1702,7 @@ __global__ __launch_bounds__(512) void k_batch(const double *T, int rows, size_t
                                              (unsigned *)nullptr);
                     if (hb && t < SX_HMAX) s_fr1[t] = __longlong_as_double((long long)fr1);
                     if (ok) {
-                        if (t < qq) s_fr[t] = gd(s_g[kRF - kRD + 2 * t], s_g[kRF - kRD + 1 + 2 * t]);
-                        if (t == 0) {
-                            s_det_dmin = gd(s_g[0], s_g[1]);
-                            s_p[q] = gd(s_g[kRA - kRD], s_g[kRA - kRD + 1]);
-                            s_br = gd(s_g[kRB - kRD], s_g[kRB - kRD + 1]);
-                            s_det_e = (int)s_g[kRE - kRD];
-                            s_det_st = (int)s_g[kRS - kRD];
-                            s_r[q] = r;
-                            s_e[q] = (int)s_g[kRE - kRD];
-                        }
+                        details_in(t, q, qq, r, s_g, s_fr, s_p, s_r, s_e, s_det_dmin, s_br, s_det_e, s_det_st);
                     }
                     if (t == 0) s_det_ok = ok;
                 }
@@ -1687,35 +1735,20 @@ __global__ __launch_bounds__(512) void k_batch(const double *T, int rows, size_t
                     u = hist_row_bc(u, qq, r, s_hist, s_fr, s_p + hb, s_r + hb);
                     s_hist[qq * SX_TILE + t] = u;
                     if (tb == 0) SX_STAMP(7);
-                    const double fd = -dmin / p;  // updateCostsVector, solver.cu:48-56
-                    if (tb == 0 && t == 0) d0 = fma(fd, br, d0);
-                    if (liveB) {
-                        dj = fma(fd, u, dj);
-                        if (cmp_eps(dj, v) < 0) {
-                            v = dj;
-                            i = ia;
-                        }
-                    }
+                    obj_update(dmin, p, br, u, tb == 0 && t == 0, liveB, ia, d0, dj, v, i);
                 }
                 // pass 1 (reduction.cu:51-80): half-wave trees, one block barrier, wave 0 combines
                 // the half winners and publishes the record alone.  (Every wave's U store of the
                 // previous pivot is acknowledged first: the ratio side reads U[s < q] from memory
                 // after seeing this record.)
-                half_argmin(v, i);
-                if ((t & 31) == 0) {
-                    s_v[t >> 5] = v;
-                    s_i[t >> 5] = i;
-                }
+                tile_halves(t, v, i, s_v, s_i);
                 drain();
                 __syncthreads();
                 if (t < 64) {
                     double wv = t < 16 ? s_v[t] : DBL_MAX;
                     int wi = t < 16 ? s_i[t] : -1;
                     half_argmin(wv, wi);
-                    wi = __builtin_amdgcn_readfirstlane(wi);
-                    const long long vb = __double_as_longlong(wv);
-                    wv = __longlong_as_double(((long long)__builtin_amdgcn_readfirstlane((int)(vb >> 32)) << 32) |
-                                              (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)vb));
+                    wave_uniform(wv, wi);
                     const int win = wi >= 0 ? wi - tb * SX_TILE : 0;
                     // the record: the winner's d value (payload: its index in the tile) and its pivot-row
                     // value of this pivot U[q][w] (the ratio side's newest pending entry of the entering
@@ -1918,8 +1951,30 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
         // the entering column's stored value of this row: loaded as soon as the entering
         // variable is known, so the load overlaps the wait for its pending history
         double a_pre = liveA ? T[tl.idx(li, c.map(1 + (e >= 0 ? e : 0)))] : 0.0;
-        // The two roles run separate loops (the same steps per pivot, as k_batch), so neither
-        // role's registers are held across the other's code.
+        // The stage switch at slot SX_HMAX (k_batch's next_stage at system scope), once for both role
+        // loops: this thread's first-stage history to registers, the LDS history reused.  Every
+        // thread's stores acknowledged -- the objective tiles' U rows (write-through into every rank),
+        // the ratio tiles' F -- then one system-scope release writes this device's L2 back, before any
+        // second-stage record: a block that has seen one reads the first stage's U[s][e] (its own
+        // rank's U) and F[r][s] (the owner's F) with system-scope loads.  (A macro: as a lambda or a
+        // function it moves the two kernels' instructions)
+#define SX_MR_NEXT_STAGE()                                                                         \
+    do {                                                                                           \
+        _Pragma("unroll") for (int s1 = 0; s1 < SX_HMAX; ++s1) h1[s1] = s_hist[s1 * SX_TILE + t]; \
+        bits1 = bits;                                                                              \
+        bits = 0u;                                                                                 \
+        if (t < SX_HMAX) s_ue1[t] = s_ue[t]; /* U[s][e] of pivot SX_HMAX: its objective record */  \
+        drain();                                                                                   \
+        __syncthreads();                                                                           \
+        if (t == 0) {                                                                              \
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                                          \
+            drain();                                                                               \
+        }                                                                                          \
+        __syncthreads();                                                                           \
+        hb = SX_HMAX;                                                                              \
+    } while (0)
+        // The two roles run separate loops (the same steps per pivot), so neither role's registers
+        // are held across the other's code.
         if (isA) {
             for (int q = 0; q < K; ++q) {
                 const unsigned tag = make_tag(B, q);
@@ -1927,32 +1982,12 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
                     status = SX_PIVOT_CAP;
                     break;
                 }
-                if (inj != 0u && isA && rank == 0 && bid == 0 && (unsigned)q + 1u == inj) {  // test hook
+                if (inj != 0u && rank == 0 && bid == 0 && (unsigned)q + 1u == inj) {  // test hook
                     if (t == 0) __hip_atomic_store(&ch->abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     aborted = true;
                     break;
                 }
-                if (q == SX_HMAX) {
-                    // the stage switch (k_batch's, at system scope): this thread's first-stage history
-                    // to registers, the LDS history reused.  Every thread's stores acknowledged -- the
-                    // objective tiles' U rows (write-through into every rank), the ratio tiles' F --
-                    // then one system-scope release writes this device's L2 back, before any
-                    // second-stage record: a block that has seen one reads the first stage's U[s][e]
-                    // (its own rank's U) and F[r][s] (the owner's F) with system-scope loads
-    #pragma unroll
-                    for (int s1 = 0; s1 < SX_HMAX; ++s1) h1[s1] = s_hist[s1 * SX_TILE + t];
-                    bits1 = bits;
-                    bits = 0u;
-                    if (t < SX_HMAX) s_ue1[t] = s_ue[t];  // (U[s][e] of pivot SX_HMAX: its objective record)
-                    drain();
-                    __syncthreads();
-                    if (t == 0) {
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-                        drain();
-                    }
-                    __syncthreads();
-                    hb = SX_HMAX;
-                }
+                if (q == SX_HMAX) SX_MR_NEXT_STAGE();
                 const int qq = q - hb;  // slot within the stage
                 const bool done = !(cmp_eps(dmin, 0.0) < 0);  // solver.cu:88: optimal
                 double a1 = a_pre;
@@ -1970,7 +2005,7 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
                 }
                 s_a[t] = a;
                 s_b[t] = b;
-                // pass 1: half-wave trees, one block barrier, wave 0 combines and publishes (k_batch)
+                // pass 1: half-wave trees, one block barrier, wave 0 combines and publishes
                 half_argmin(rv, ri);
                 const int anyw = __ballot(elig) != 0ull;
                 if ((t & 31) == 0) {
@@ -1986,10 +2021,7 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
                     int any = 0;
 #pragma unroll
                     for (int w = 0; w < SX_TILE / 64; ++w) any |= s_welig[w];
-                    wi = __builtin_amdgcn_readfirstlane(wi);
-                    const long long vb = __double_as_longlong(wv);
-                    wv = __longlong_as_double(((long long)__builtin_amdgcn_readfirstlane((int)(vb >> 32)) << 32) |
-                                              (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)vb));
+                    wave_uniform(wv, wi);
                     const int wl = wi >= 0 ? wi - row0 - bid * SX_TILE : 0;
                     // the record into every rank's copy
                     const unsigned pl = (wi >= 0 ? (unsigned)(wi - gt * SX_TILE) : SX_NOIDX) | ((unsigned)any << 10);
@@ -2081,11 +2113,8 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
                         b = fma(f, br, b);
                     }
                 }
-                if (bid == 0 && t == 0) {  // every rank keeps the whole basis and the records
-                    recs[q].r = r;         // (base[r] = e, solver.cu:105: at the end of the batch)
-                    recs[q].e = e;
-                    recs[q].p = p;
-                    U[(size_t)q * ld] = br;
+                if (bid == 0 && t == 0) {  // (every rank keeps the whole basis and the records)
+                    record_pivot(recs, U, ld, q, r, e, p, br);
                 }
                 e = enext;
                 dmin = s_ent_v;
@@ -2099,32 +2128,7 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
                     status = SX_PIVOT_CAP;
                     break;
                 }
-                if (inj != 0u && isA && rank == 0 && bid == 0 && (unsigned)q + 1u == inj) {  // test hook
-                    if (t == 0) __hip_atomic_store(&ch->abort_w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    aborted = true;
-                    break;
-                }
-                if (q == SX_HMAX) {
-                    // the stage switch (k_batch's, at system scope): this thread's first-stage history
-                    // to registers, the LDS history reused.  Every thread's stores acknowledged -- the
-                    // objective tiles' U rows (write-through into every rank), the ratio tiles' F --
-                    // then one system-scope release writes this device's L2 back, before any
-                    // second-stage record: a block that has seen one reads the first stage's U[s][e]
-                    // (its own rank's U) and F[r][s] (the owner's F) with system-scope loads
-    #pragma unroll
-                    for (int s1 = 0; s1 < SX_HMAX; ++s1) h1[s1] = s_hist[s1 * SX_TILE + t];
-                    bits1 = bits;
-                    bits = 0u;
-                    if (t < SX_HMAX) s_ue1[t] = s_ue[t];  // (U[s][e] of pivot SX_HMAX: its objective record)
-                    drain();
-                    __syncthreads();
-                    if (t == 0) {
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-                        drain();
-                    }
-                    __syncthreads();
-                    hb = SX_HMAX;
-                }
+                if (q == SX_HMAX) SX_MR_NEXT_STAGE();
                 const int qq = q - hb;  // slot within the stage
                 // ---- selection: pass 2 over every rank's ratio tiles (wave 0 polls and reduces)
                 if (t < 64) {
@@ -2168,16 +2172,7 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
                                                                     timeout, (unsigned *)nullptr);
                     if (hb && t < SX_HMAX) s_fr1[t] = __longlong_as_double((long long)fr1);
                     if (ok) {
-                        if (t < qq) s_fr[t] = gd(s_g[kRF - kRD + 2 * t], s_g[kRF - kRD + 1 + 2 * t]);
-                        if (t == 0) {
-                            s_det_dmin = gd(s_g[0], s_g[1]);
-                            s_p[q] = gd(s_g[kRA - kRD], s_g[kRA - kRD + 1]);
-                            s_br = gd(s_g[kRB - kRD], s_g[kRB - kRD + 1]);
-                            s_det_e = (int)s_g[kRE - kRD];
-                            s_det_st = (int)s_g[kRS - kRD];
-                            s_r[q] = r;
-                            s_e[q] = (int)s_g[kRE - kRD];
-                        }
+                        details_in(t, q, qq, r, s_g, s_fr, s_p, s_r, s_e, s_det_dmin, s_br, s_det_e, s_det_st);
                     }
                     if (t == 0) s_det_ok = ok;
                 }
@@ -2206,30 +2201,15 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
                     if (hb) u = stage1_row_rl(u, h1, r, s_fr1, s_p, s_r);
                     u = hist_row_rl(u, qq, r, s_hist, s_fr, s_p + hb, s_r + hb);
                     s_hist[qq * SX_TILE + t] = u;
-                    const double fd = -dmin / p;  // updateCostsVector, solver.cu:48-56
-                    if (tb == 0 && t == 0) d0 = fma(fd, br, d0);
-                    if (liveB) {
-                        dj = fma(fd, u, dj);
-                        if (cmp_eps(dj, v) < 0) {
-                            v = dj;
-                            i = ia;
-                        }
-                    }
+                    obj_update(dmin, p, br, u, tb == 0 && t == 0, liveB, ia, d0, dj, v, i);
                 }
-                half_argmin(v, i);
-                if ((t & 31) == 0) {
-                    s_v[t >> 5] = v;
-                    s_i[t >> 5] = i;
-                }
+                tile_halves(t, v, i, s_v, s_i);
                 __syncthreads();
-                if (t < 64) {  // wave 0 combines the half winners and publishes (k_batch)
+                if (t < 64) {  // wave 0 combines the half winners and publishes
                     double wv = t < 16 ? s_v[t] : DBL_MAX;
                     int wi = t < 16 ? s_i[t] : -1;
                     half_argmin(wv, wi);
-                    wi = __builtin_amdgcn_readfirstlane(wi);
-                    const long long vb = __double_as_longlong(wv);
-                    wv = __longlong_as_double(((long long)__builtin_amdgcn_readfirstlane((int)(vb >> 32)) << 32) |
-                                              (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)vb));
+                    wave_uniform(wv, wi);
                     const int win = wi >= 0 ? wi - tb * SX_TILE : 0;
                     const unsigned pl = wi >= 0 ? (unsigned)win : SX_NOIDX;
                     // granule-major over the ranks: the value granules reach every rank first
@@ -2347,6 +2327,7 @@ __device__ __forceinline__ void batch_mr_body(int bid, unsigned nbl, const doubl
     }
     st->e_next = e;
     st->dmin_next = dmin;
+#undef SX_MR_NEXT_STAGE
 }
 
 

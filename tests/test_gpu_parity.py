@@ -357,6 +357,18 @@ def test_p2p_fused_virtual_ranks(gpu, batch, W):
     assert same(Tg, T) and same(dg, d) and np.array_equal(bg, base)
 
 
+@pytest.mark.parametrize("W", [1, 2, 3])
+def test_fused_pivot_cap_in_second_stage(gpu, W):
+    """the pivot cap falling inside the second stage of a fused batch (slot 36 of the second
+    64-pivot batch), one shard and peer-memory shards: the batch ends without a decision of the
+    ratio side, past the stage switch, and is committed and swept as far as it got"""
+    T, d, base = _phase1_state(300, 1100, 11)
+    Tg, dg, bg, st, done = _pivots_with({"batch": 64, "W": W, "p2p": 1 if W > 1 else -1}, T, d, base, 100)
+    st_o, done_o = oracle.solve(T, d, base, max_pivots=100)
+    assert done == done_o == 100
+    assert same(Tg, T) and same(dg, d) and np.array_equal(bg, base)
+
+
 @pytest.mark.parametrize("batch", [32, 64])
 @pytest.mark.parametrize("single", [1, 0])
 @pytest.mark.parametrize("W", [2, 3])
