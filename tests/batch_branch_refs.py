@@ -24,16 +24,18 @@ def explicit(root_inst, var, coef, rhs):
     return (np.ascontiguousarray(np.vstack([A, rows])), np.concatenate([b, np.asarray(rhs, dtype=np.float64)]), c)
 
 
-def ref_branch(state, root_inst, var, coef, rhs, max_pivots=-1):
+def ref_branch(state, root_inst, var, coef, rhs, max_pivots=-1, argmin=oracle.argmin, enter_argmin=None,
+               leave_argmin=None):
     """the state and results of the child of `state` (left as it is): the bound rows that `state` does
-    not hold yet -- for the entry that is the last one alone -- appended one at a time by ref_rows"""
+    not hold yet -- for the entry that is the last one alone -- appended one at a time by ref_rows, which
+    takes the selections argmin, enter_argmin and leave_argmin"""
     mA = root_inst[0].shape[0]
     q = len(var)
     have = state["T"].shape[0] - mA
     assert 0 <= have < q and len(coef) == q and len(rhs) == q
     for t in range(have, q):
         A, b, c = explicit(root_inst, var[:t + 1], coef[:t + 1], rhs[:t + 1])
-        state = ref_rows(state, A, b, c, max_pivots)
+        state = ref_rows(state, A, b, c, max_pivots, argmin, enter_argmin, leave_argmin)
     return state
 
 

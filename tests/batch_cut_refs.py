@@ -87,10 +87,11 @@ def in_callers_variables(g, f0, A0, b0):
     return acc[:n].copy(), float(acc[n])
 
 
-def ref_cut(state, A0, b0, c, integer, q, away=AWAY, rows=None, max_pivots=-1):
+def ref_cut(state, A0, b0, c, integer, q, away=AWAY, rows=None, max_pivots=-1, argmin=oracle.argmin):
     """(cut_A [q, n], cut_b [q], cut_row int32 [q], ref_rows of the grown problem) of `state` (shape
     (n, m0), left as it is), solved with A0 [m0, n], b0 [m0]; integer: a mask [n]; rows: the caller's
-    source rows [q] or None"""
+    source rows [q] or None; argmin: the selection of the source row, the oracle's eps-argmin tree unless
+    a test swaps it"""
     m0, n = A0.shape
     assert state["T"].shape == (m0, 1 + n + m0) and q >= 1
     integer = np.asarray(integer).astype(bool)
@@ -101,7 +102,7 @@ def ref_cut(state, A0, b0, c, integer, q, away=AWAY, rows=None, max_pivots=-1):
         for t in range(q):
             keys = row_keys(state, integer, away, taken)
             if rows is None:
-                r, v = oracle.argmin(keys)
+                r, v = argmin(keys)
                 if v == DBL_MAX or r < 0:
                     continue
             else:

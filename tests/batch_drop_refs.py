@@ -44,9 +44,11 @@ def _without(T, d, base, row, col, v):
     return T, d, np.where(base > v, base - 1, base).astype(np.int32)
 
 
-def ref_drop(state, kind, idx, A, b, c, max_pivots=-1):
+def ref_drop(state, kind, idx, A, b, c, max_pivots=-1, argmin=oracle.argmin):
     """the reduced state and results of `state` (left as it is) with the rows (kind ROWS) or columns (kind
-    COLS) idx -- strictly ascending -- taken out; A [m, n], b [m], c [n] are the reduced problem"""
+    COLS) idx -- strictly ascending -- taken out; A [m, n], b [m], c [n] are the reduced problem; argmin: the
+    selection of a forced pivot (the primal ratio of ROWS, the dual entering ratio of COLS), the oracle's
+    eps-argmin tree unless a test swaps it"""
     m0, Ns0 = state["T"].shape
     n0 = Ns0 - 1 - m0
     idx = [int(v) for v in idx]
@@ -80,7 +82,7 @@ def ref_drop(state, kind, idx, A, b, c, max_pivots=-1):
                     else:
                         why = "no-candidate"
                         break
-                    r, _ = oracle.argmin(np.array([oracle.ratio(T[i, 0], a[i]) for i in range(m)]))
+                    r, _ = argmin(np.array([oracle.ratio(T[i, 0], a[i]) for i in range(m)]))
                     if r < 0 or r >= m:
                         why = "no-candidate"
                         break
@@ -99,8 +101,8 @@ def ref_drop(state, kind, idx, A, b, c, max_pivots=-1):
                     if not elig.any():
                         why = "no-candidate"
                         break
-                    e, _ = oracle.argmin(np.array([DBL_MAX if j == v else oracle.ratio(d[1 + j], a[j])
-                                                   for j in range(n + m)]))
+                    e, _ = argmin(np.array([DBL_MAX if j == v else oracle.ratio(d[1 + j], a[j])
+                                            for j in range(n + m)]))
                     if e < 0 or e >= n + m:
                         why = "no-candidate"
                         break

@@ -45,21 +45,23 @@ def dual_feasible(state):
     return not _negative(oracle.argmin(state["d"][1:Ns])[1])
 
 
-def _dual(T, d, base, k0, max_pivots, argmin):
+def _dual(T, d, base, k0, max_pivots, argmin, enter_argmin=None, leave_argmin=None):
     """the dual loop on T [m, Ns], d [Ns], base, behind k0 pivots: (status or None when the loop was
-    left, pivots); all three are written"""
+    left, pivots); all three are written.  enter_argmin / leave_argmin: the selection of the entering
+    ratio / of the leaving row alone (None: argmin)"""
     m, Ns = T.shape
+    enter_argmin, leave_argmin = enter_argmin or argmin, leave_argmin or argmin
     k = k0
     while True:
         if max_pivots >= 0 and k >= max_pivots:
             return oracle.PIVOT_CAP, k
-        r, bmin = argmin(T[:, 0])
+        r, bmin = leave_argmin(T[:, 0])
         if not _negative(bmin):
             return None, k
         neg = -T[r, 1:]
         if not (neg >= EPS).any():
             return oracle.INFEASIBLE, k
-        e, _ = argmin(np.array([oracle.ratio(d[1 + j], neg[j]) for j in range(Ns - 1)]))
+        e, _ = enter_argmin(np.array([oracle.ratio(d[1 + j], neg[j]) for j in range(Ns - 1)]))
         if e < 0 or e >= Ns - 1:
             return NUMERIC_FAIL, k
         prow, colE = T[r].copy(), T[:, 1 + e].copy()
@@ -68,12 +70,12 @@ def _dual(T, d, base, k0, max_pivots, argmin):
         k += 1
 
 
-def _enter_dual(T, d, base, pivots, c, max_pivots, argmin):
+def _enter_dual(T, d, base, pivots, c, max_pivots, argmin, enter_argmin=None, leave_argmin=None):
     """the dual loop at pivots[1], then phase 2 at the same count; T [m, Ns], d at full width"""
     m, Ns = T.shape
     n = Ns - 1 - m
     d2 = d[:Ns].copy()
-    status, k = _dual(T, d2, base, pivots[1], max_pivots, argmin)
+    status, k = _dual(T, d2, base, pivots[1], max_pivots, argmin, enter_argmin, leave_argmin)
     d[:Ns] = d2
     d[Ns:] = 0.0
     if status is None:
@@ -85,22 +87,24 @@ def _enter_dual(T, d, base, pivots, c, max_pivots, argmin):
     return res
 
 
-def ref_rhs(state, A, b, c, max_pivots=-1, argmin=oracle.argmin):
+def ref_rhs(state, A, b, c, max_pivots=-1, argmin=oracle.argmin, enter_argmin=None, leave_argmin=None):
     """the state and results of a re-solve of `state` (left as it is) for the right-hand side b;
-    argmin: the selection of the dual loop, the oracle's eps-argmin tree unless a test swaps it"""
+    argmin: the selection of the dual loop, the oracle's eps-argmin tree unless a test swaps it;
+    enter_argmin / leave_argmin: one for the entering ratio / the leaving row alone (None: argmin)"""
     if state["phase"] == 1 or not dual_feasible(state):
         return ref_state(A, b, c, max_pivots)  # the cold start (shared: do not write it)
     T, d, base = state["T"].copy(), state["d"].copy(), state["base"].copy()
     T[:, 0], d[0] = new_rhs(state, b)
-    return _enter_dual(T, d, base, (state["pivots"][0], 0), c, max_pivots, argmin)
+    return _enter_dual(T, d, base, (state["pivots"][0], 0), c, max_pivots, argmin, enter_argmin, leave_argmin)
 
 
-def ref_rhs_resume(state, c, max_pivots=-1):
-    """the plain resume (rerhs = 0): phases 1 and 2 are the state entry's, phase 3 re-enters the dual loop"""
+def ref_rhs_resume(state, c, max_pivots=-1, argmin=oracle.argmin, enter_argmin=None, leave_argmin=None):
+    """the plain resume (rerhs = 0): phases 1 and 2 are the state entry's, phase 3 re-enters the dual loop
+    (argmin, enter_argmin, leave_argmin: that loop's selections, as in ref_rhs)"""
     if state["phase"] != 3:
         return ref_resume(state, c, max_pivots)
     return _enter_dual(state["T"].copy(), state["d"].copy(), state["base"].copy(), state["pivots"], c, max_pivots,
-                       oracle.argmin)
+                       argmin, enter_argmin, leave_argmin)
 
 
 # ---- the instances both test files use ----

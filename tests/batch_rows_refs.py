@@ -47,9 +47,10 @@ def grown_dual_feasible(state, q):
     return not _negative(oracle.argmin(np.concatenate([state["d"][1:Ns0], np.zeros(q)]))[1])
 
 
-def ref_rows(state, A, b, c, max_pivots=-1):
+def ref_rows(state, A, b, c, max_pivots=-1, argmin=oracle.argmin, enter_argmin=None, leave_argmin=None):
     """the grown state and results of `state` (shape (n, m0), left as it is) with the rows m0 .. m of
-    A [m, n] and b [m] appended"""
+    A [m, n] and b [m] appended; argmin: the selection of the dual loop, enter_argmin / leave_argmin: one
+    for its entering ratio / its leaving row alone (batch_rhs_refs.ref_rhs)"""
     m0, Ns0 = state["T"].shape
     m, n = A.shape
     q = m - m0
@@ -63,7 +64,7 @@ def ref_rows(state, A, b, c, max_pivots=-1):
     d = np.zeros(Ns + m)
     d[:Ns0] = state["d"][:Ns0]
     base = np.concatenate([state["base"], n + m0 + np.arange(q)]).astype(np.int32)
-    return _enter_dual(T, d, base, (state["pivots"][0], 0), c, max_pivots, oracle.argmin)
+    return _enter_dual(T, d, base, (state["pivots"][0], 0), c, max_pivots, argmin, enter_argmin, leave_argmin)
 
 
 # ---- the instances both test files use ----
